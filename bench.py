@@ -5,10 +5,16 @@ resident in HBM: encode the read text (gwa_batch_run starts from it, as the refe
 call starts from the Read's String), fm_quickscan + bsf_search tiers, and the SAM text of every read
 written in HBM (gwa_batch_format; A/Align.java:187-195 -> A/SAMOutput.java:73-82).  Weak scaling:
 every rank holds a full index replica on its own GPU and aligns its own shard; value = total reads
-of all ranks / max-over-ranks time.  At N = 1 the default run adds detail.hg19r, the same step on the
-hg19-like repetitive genome.
+of all ranks / max-over-ranks time.
 
-  python bench.py [--gpus N --steps K --warmup W] [--genome hg19|hg19r|ecoli|<Mbp>] [--reads R]
+A plain run does what that figure needs and no more: genome, index, reads, W warm-up and K timed
+steps, the result line.  --full adds everything else the line can carry, outside the timed region:
+the oracle parity check, the CPU baselines, the host-pipeline, end-to-end and host-ceiling legs, the
+multi-GPU SAM gather and, at N = 1, detail.hg19r (the same step on the hg19-like repetitive genome).
+--dump-outputs DIR writes what the last timed step computed as .npy files (dump_outputs).
+
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+                  [--genome hg19|hg19r|ecoli|<Mbp>] [--reads R]
 
 --gpus N > 1 without a torch.distributed environment re-launches this script under
 `torch.distributed.run` with N ranks (before anything touches the GPU); ranks beyond the visible GPU
@@ -32,8 +38,11 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 JSON_OUT = sys.stdout
 
 
+T_START = time.time()
+
+
 def log(*a):
-    print("[bench]", *a, file=sys.stderr, flush=True)
+    print("[bench] %6.1fs" % (time.time() - T_START), *a, file=sys.stderr, flush=True)
 
 
 def _pmc_traffic(kernel, workload):
@@ -208,6 +217,40 @@ def timed_steps(batch, steps, warmup, barrier):
     mine = time.perf_counter() - t0
     win1 = time.clock_gettime_ns(time.CLOCK_MONOTONIC)
     return mine, [win0, win1], {k: v / max(1, steps) for k, v in acc.items()}, st, sam_bytes
+
+
+def dump_outputs(batch, out_dir, np, torch, rank=0, world=1):
+    """--dump-outputs: what the last timed step handed its caller, the batch's SAM text in HBM
+    (gwa_batch_sam_copy), as .npy files under out_dir (rank r of a multi-rank run under out_dir/rank<r>):
+      sam_bytes.npy          float64 [1]   the size of the text
+      sam_chunk_sums.npy     float64 [c]   the sum of the bytes of every 64 KiB chunk of the whole text
+                                           (exact in float64), the last chunk the remainder
+      sam_sample_offsets.npy float64 [b]   byte offsets of the sampled blocks
+      sam_sample.npy         float32 [b * 128 KiB]  the bytes of 64 blocks of the text, drawn once with a
+                                           fixed seed from the text's 128 KiB blocks (the whole text when
+                                           it is no longer than the sample); 32 MB
+    The inputs are seeded (tools/synth.py), so two builds given the same arguments can be compared
+    file for file."""
+    d = out_dir if world == 1 else os.path.join(out_dir, "rank%d" % rank)
+    os.makedirs(d, exist_ok=True)
+    t = batch.sam_device()
+    n = int(t.numel())
+    chunk, block, nblocks = 1 << 16, 1 << 17, 64
+    whole = n // chunk
+    sums = [t[:whole * chunk].view(whole, chunk).sum(dim=1, dtype=torch.int64),
+            t[whole * chunk:].sum(dtype=torch.int64).reshape(1)]
+    if n <= block * nblocks:
+        offs = np.zeros(1, dtype=np.float64)
+        sample = t
+    else:
+        pick = np.sort(np.random.default_rng(0x5A4D).choice(n // block, nblocks, replace=False))
+        offs = (pick * block).astype(np.float64)
+        sample = torch.cat([t[int(p) * block:(int(p) + 1) * block] for p in pick])
+    np.save(os.path.join(d, "sam_bytes.npy"), np.array([n], dtype=np.float64))
+    np.save(os.path.join(d, "sam_chunk_sums.npy"), torch.cat(sums).cpu().numpy().astype(np.float64))
+    np.save(os.path.join(d, "sam_sample_offsets.npy"), offs)
+    np.save(os.path.join(d, "sam_sample.npy"), sample.cpu().numpy().astype(np.float32))
+    log("outputs of the last timed step written to %s (%d bytes of SAM text)" % (d, n))
 
 
 def make_reads(synth, np, codes, lengths, n, m, c4, rank):
@@ -430,79 +473,8 @@ def hg19r_leg(args, gen, gwa, synth, np, cfg, log):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--genome", default=os.environ.get("GWA_BENCH_GENOME", "hg19"),
-                    help="hg19: hg19 contig lengths, i.i.d. ACGT with hg19-like N-gap runs (the BASELINE stand-in, "
-                         "SURVEY.md 8(d)), or the FASTA file $GWA_HG19 when set; hg19r: hg19-like repeats and N gaps "
-                         "(tools/synth.genome_repeats); ecoli (or the FASTA file $GWA_ECOLI); a size in Mbp; or the "
-                         "path of a FASTA file")
-    ap.add_argument("--reads", type=int, default=int(os.environ.get("GWA_BENCH_READS", "0")))
-    ap.add_argument("--k", type=float, default=None, help="max edits (default: 2 for c2, 5 for c4)")
-    ap.add_argument("--workload", default="c2", choices=["c2", "c4", "c5"],
-                    help="c2: 100 bp, 0-2 substitutions (the BASELINE metric); c4: 150 bp, 0-5 edits with indels; "
-                         "c5: 2x100 bp paired-end, insert ~ N(300, 30), proper pairs within [210, 390]")
-    ap.add_argument("--strategy", default="bsf", choices=["bsf", "sf"], help="-m (align strategy)")
-    ap.add_argument("--cpu-sample", type=int, default=int(os.environ.get("GWA_CPU_SAMPLE", "40000")),
-                    help="reads of the single-thread CPU baseline (SURVEY.md 8(d)(i)), each of 3 runs")
-    ap.add_argument("--cpu-threads", type=int, default=0,
-                    help="host threads of the multi-core CPU baseline (default: the cores this process may use)")
-    ap.add_argument("--cpu-seconds", type=float, default=5.0,
-                    help="target duration of each of the 3 multi-core CPU baseline runs (sample sized from the 1-thread rate)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--check", type=int, default=20000,
-                    help="random reads of step 0 checked against the oracle (plus every read a search tier >= 1 ran)")
-    ap.add_argument("--no-pipeline", action="store_true", help="skip the host-pipeline (FASTQ-to-SAM) leg")
-    ap.add_argument("--no-hg19r", action="store_true", help="skip the detail.hg19r leg (default C2 run at N=1 only)")
-    args = ap.parse_args()
-
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        spawn_ranks(args)
-    # stdout carries exactly one JSON line (rank 0): whatever else writes to fd 1 in this process or
-    # its children -- torch / gloo / RCCL C++ logging such as "[Gloo] Rank 0 is connected to 1 peer
-    # ranks" -- is sent to stderr
-    global JSON_OUT
-    sys.stdout.flush()
-    JSON_OUT = os.fdopen(os.dup(1), "w")
-    os.dup2(2, 1)
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world != args.gpus and "WORLD_SIZE" in os.environ:
-        raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    c4 = args.workload == "c4"
-    # the hg19r leg's genome is generated by a child process (started before this process touches
-    # the GPU) while the main leg runs
-    gen = None
-    if (world == 1 and args.workload == "c2" and args.genome == "hg19" and not args.no_hg19r and args.strategy == "bsf"
-            and args.k in (None, 2.0) and not os.path.isfile(os.environ.get("GWA_HG19", ""))):
-        import subprocess
-        import tempfile
-        import shutil
-        d = "/dev/shm" if os.path.isdir("/dev/shm") and shutil.disk_usage("/dev/shm").free > (8 << 30) else tempfile.gettempdir()
-        path = os.path.join(d, "gwa_bench_hg19r_%d.npy" % os.getpid())
-        gen = (subprocess.Popen([sys.executable, os.path.join(REPO, "tools", "synth.py"), "hg19r", path]), path)
-
-    import numpy as np
-    import synth
-    import gwa
-    import dist as gdist
-
-    dist = world > 1
-    if dist:
-        import torch
-        import torch.distributed as tdist
-        # CPU tensors (timings, barriers) over gloo; the optional SAM gather of device buffers over RCCL
-        # (nccl) when every rank has a GPU of its own (torch.cuda.device_count does not initialise the GPU)
-        tdist.init_process_group("cpu:gloo,cuda:nccl" if torch.cuda.device_count() >= world else "gloo")
-    import torch
-    dev = gdist.device_for(local, torch.cuda.device_count())
-    torch.cuda.set_device(dev)
-
-    t0 = time.time()
+def make_genome(args, synth):
+    """The genome --genome names -> (codes, names, lengths, description, path of the real FASTA or None)"""
     # a real genome when one is given: --genome <FASTA path>, or $GWA_HG19 / $GWA_ECOLI for hg19 / ecoli
     # (BASELINE.md, SURVEY.md 8(d)); the reads stay synthetic, drawn from it
     real = None
@@ -530,13 +502,107 @@ def main():
         mb = float(args.genome)
         codes, names, lengths = synth.genome([("chr%d" % (i + 1), int(mb * 1e6 / 4)) for i in range(4)], config_id=1)
         gname = "%g Mbp synthetic (4 contigs, i.i.d. ACGT)" % mb
+    return codes, names, lengths, gname, real
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--genome", default=os.environ.get("GWA_BENCH_GENOME", "hg19"),
+                    help="hg19: hg19 contig lengths, i.i.d. ACGT with hg19-like N-gap runs (the BASELINE stand-in, "
+                         "SURVEY.md 8(d)), or the FASTA file $GWA_HG19 when set; hg19r: hg19-like repeats and N gaps "
+                         "(tools/synth.genome_repeats); ecoli (or the FASTA file $GWA_ECOLI); a size in Mbp; or the "
+                         "path of a FASTA file")
+    ap.add_argument("--reads", type=int, default=int(os.environ.get("GWA_BENCH_READS", "0")))
+    ap.add_argument("--k", type=float, default=None, help="max edits (default: 2 for c2, 5 for c4)")
+    ap.add_argument("--workload", default="c2", choices=["c2", "c4", "c5"],
+                    help="c2: 100 bp, 0-2 substitutions (the BASELINE metric); c4: 150 bp, 0-5 edits with indels; "
+                         "c5: 2x100 bp paired-end, insert ~ N(300, 30), proper pairs within [210, 390]")
+    ap.add_argument("--strategy", default="bsf", choices=["bsf", "sf"], help="-m (align strategy)")
+    ap.add_argument("--cpu-sample", type=int, default=int(os.environ.get("GWA_CPU_SAMPLE", "40000")),
+                    help="reads of the single-thread CPU baseline (SURVEY.md 8(d)(i)), each of 3 runs")
+    ap.add_argument("--cpu-threads", type=int, default=0,
+                    help="host threads of the multi-core CPU baseline (default: the cores this process may use)")
+    ap.add_argument("--cpu-seconds", type=float, default=5.0,
+                    help="target duration of each of the 3 multi-core CPU baseline runs (sample sized from the 1-thread rate)")
+    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--check", type=int, default=20000,
+                    help="random reads of step 0 checked against the oracle (plus every read a search tier >= 1 ran)")
+    ap.add_argument("--no-pipeline", action="store_true", help="skip the host-pipeline (FASTQ-to-SAM) leg")
+    ap.add_argument("--no-hg19r", action="store_true", help="skip the detail.hg19r leg (default C2 run at N=1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, outside the timed region: oracle parity, CPU "
+                         "baselines, host-pipeline / end-to-end / host-ceiling legs, the multi-GPU SAM gather, detail.hg19r "
+                         "(--check, --no-cpu, --no-pipeline, --no-hg19r and the --cpu-* options select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the SAM text in HBM: size, per-chunk "
+                         "byte sums, a fixed seeded sample) as DIR/<name>.npy")
+    args = ap.parse_args()
+
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        spawn_ranks(args)
+    # stdout carries exactly one JSON line (rank 0): whatever else writes to fd 1 in this process or
+    # its children -- torch / gloo / RCCL C++ logging such as "[Gloo] Rank 0 is connected to 1 peer
+    # ranks" -- is sent to stderr
+    global JSON_OUT
+    sys.stdout.flush()
+    JSON_OUT = os.fdopen(os.dup(1), "w")
+    os.dup2(2, 1)
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world != args.gpus and "WORLD_SIZE" in os.environ:
+        raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    c4 = args.workload == "c4"
+    # the hg19r leg's genome is generated by a child process (started before this process touches
+    # the GPU) while the main leg runs
+    gen = None
+    if (args.full and world == 1 and args.workload == "c2" and args.genome == "hg19" and not args.no_hg19r
+            and args.strategy == "bsf" and args.k in (None, 2.0) and not os.path.isfile(os.environ.get("GWA_HG19", ""))):
+        import subprocess
+        import tempfile
+        import shutil
+        d = "/dev/shm" if os.path.isdir("/dev/shm") and shutil.disk_usage("/dev/shm").free > (8 << 30) else tempfile.gettempdir()
+        path = os.path.join(d, "gwa_bench_hg19r_%d.npy" % os.getpid())
+        gen = (subprocess.Popen([sys.executable, os.path.join(REPO, "tools", "synth.py"), "hg19r", path]), path)
+
+    import numpy as np
+    import synth
+    # set-up off the critical path: the genome is generated by a thread while torch and the library load,
+    # the reads by one while the index is built (numpy and the library's calls release the interpreter lock)
+    from concurrent.futures import ThreadPoolExecutor
+    side = ThreadPoolExecutor(1)
+    t0 = time.time()
+    genome_job = side.submit(make_genome, args, synth)
+    import gwa
+    import dist as gdist
+
+    dist = world > 1
+    if dist:
+        import torch
+        import torch.distributed as tdist
+        # CPU tensors (timings, barriers) over gloo; the optional SAM gather of device buffers over RCCL
+        # (nccl) when every rank has a GPU of its own (torch.cuda.device_count does not initialise the GPU)
+        tdist.init_process_group("cpu:gloo,cuda:nccl" if torch.cuda.device_count() >= world else "gloo")
+    import torch
+    dev = gdist.device_for(local, torch.cuda.device_count())
+    torch.cuda.set_device(dev)
+    log("modules imported")
+
+    codes, names, lengths, gname, real = genome_job.result()
     data_label = ("synthetic reads from the real genome %s" % real) if real else "synthetic"
     if args.k is None:
         args.k = 5.0 if c4 else 2.0
     reads_per_step = args.reads or (1_000_000 if c4 else 10_000_000 if (args.genome.startswith("hg19") or len(codes) > 1e9)
                                     else 1_000_000)
     log("rank %d/%d on GPU %d: genome %d bp generated in %.1fs" % (rank, world, dev, len(codes), time.time() - t0))
+    m = 150 if c4 else 100
     t0 = time.time()
+    reads_job = None
+    if args.workload != "c5":
+        reads_job = side.submit(make_reads, synth, np, codes, lengths, reads_per_step, m, c4, rank)
     gi = gwa.FMIndexOnGenome.buildFromCodes(codes, names, lengths, device=dev)
     t_index = time.time() - t0
     index_gb = gi.deviceBytes() / 1e9
@@ -545,11 +611,9 @@ def main():
     cfg = gwa.AlignmentConfig(k=args.k, strategy=args.strategy)
     if args.workload == "c5":
         return bench_c5(args, gi, codes, names, lengths, gname, rank, world, dist, dev, t_index)
-    m = 150 if c4 else 100
-    t0 = time.time()
-    blobs = make_reads(synth, np, codes, lengths, reads_per_step, m, c4, rank)
+    blobs = reads_job.result()
     name_blob, name_off, seq_blob, seq_off, qual_blob, _ = blobs
-    log("reads generated in %.1fs" % (time.time() - t0))
+    log("reads generated (alongside the index build): %.1fs after its start" % (time.time() - t0))
     t0 = time.time()
     batch = gwa.Batch(gi, cfg, blobs=blobs)
     log("batch resident in HBM: %.1fs" % (time.time() - t0))
@@ -564,11 +628,13 @@ def main():
     mine, window, kms, st, sam_bytes = timed_steps(batch, args.steps, args.warmup, barrier)
     rank_times = gdist.all_gather_floats(mine)
     dt = max(rank_times)
+    if args.dump_outputs:
+        dump_outputs(batch, args.dump_outputs, np, torch, rank, world)
 
     # SURVEY.md §8e's optional collective, outside the timed region: the SAM text of the last step, in
     # HBM on every rank, gathered in rank order (= input order) over RCCL / xGMI
     gather = None
-    if dist and torch.cuda.device_count() >= world:
+    if args.full and dist and torch.cuda.device_count() >= world:
         # every rank first agrees that its text is ready (a rank that fails to copy it would leave the
         # others blocked inside the collective)
         try:
@@ -596,14 +662,14 @@ def main():
             if merged is not None and int(merged.numel()) != int(sum(tot)):
                 gather["error"] = "merged size differs from the sum of the ranks' SAM sizes"
             del merged, mine_t
-    elif dist:
+    elif args.full and dist:
         gather = {"skipped": "ranks share a GPU (RCCL needs one GPU per rank)"}
 
     # host pipeline (first bullet): the whole path for one batch outside the timed
     # region -- reads from host memory to HBM (batch create), kernels, SAM text to the host -- reported
     # beside `value`, never as it
     pipe = None
-    if rank == 0 and not args.no_pipeline:
+    if args.full and rank == 0 and not args.no_pipeline:
         t0 = time.perf_counter()
         b2 = gwa.Batch(gi, cfg, blobs=blobs)
         t1 = time.perf_counter()
@@ -622,7 +688,7 @@ def main():
     # the library pipeline (gwa_pipeline_align_file: read, frame, H2D, parse + encode + align + SAM on
     # the GPU, D2H, write) -> a SAM file; index load excluded
     e2e = None
-    if rank == 0 and not args.no_pipeline and not c4:
+    if args.full and rank == 0 and not args.no_pipeline and not c4:
         import tempfile
         d = tempfile.mkdtemp(dir=os.environ.get("TMPDIR", "/tmp"))
         fq, so = os.path.join(d, "reads.fq"), os.path.join(d, "out.sam")
@@ -674,21 +740,19 @@ def main():
         os.rmdir(d)
 
     hostc = None
-    if rank == 0 and world == 1 and not args.no_pipeline and not c4:
+    if args.full and rank == 0 and world == 1 and not args.no_pipeline and not c4:
         hostc = host_ceiling_leg(args, gwa, synth, np, log)
 
-    counters = batch.read_counters()  # also fetches the records (stats below)
     st = batch.stats()
     total_reads = reads_per_step * args.steps * world
     value = total_reads / dt
-    deep = np.nonzero(counters[:, 12] >= 1)[0]
 
     # parity (checker only): a random sample of this rank's reads plus every read a search tier >= 1
     # ran, GPU SAM against the oracle.  The oracle index takes the GPU suffix arrays only after a
     # complete independent check of them (permutation + every adjacent pair, oracle C++).
     parity = None
     oi = None
-    if rank == 0 and (args.check or (not args.no_cpu and args.cpu_sample > 0)):
+    if args.full and rank == 0 and (args.check or (not args.no_cpu and args.cpu_sample > 0)):
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         import oracle as O
         t0 = time.time()
@@ -700,7 +764,8 @@ def main():
         oi = O.Index.from_arrays(codes, names, lengths, sa_f=sa_f, sa_r=sa_r)
         del sa_f, sa_r
         t_oidx = time.time() - t0 - t_sa
-    if args.check and rank == 0:
+    if args.full and args.check and rank == 0:
+        deep = np.nonzero(batch.read_counters()[:, 12] >= 1)[0]
         rng = np.random.default_rng(7)
         samp = np.unique(np.concatenate([rng.choice(reads_per_step, min(args.check, reads_per_step), replace=False),
                                          deep])).astype(np.uint32)
@@ -715,7 +780,7 @@ def main():
         log("parity on %d reads (%d from tiers >= 1): %s (oracle index %.1fs)" % (len(samp), len(deep), got == exp, t_oidx))
 
     cpu = cpu1 = None
-    if rank == 0 and not args.no_cpu and args.cpu_sample > 0:
+    if args.full and rank == 0 and not args.no_cpu and args.cpu_sample > 0:
         cpu, cpu1 = cpu_baselines(oi, read_tuple, reads_per_step, gwa.STRATEGIES[args.strategy], args.k, args, O,
                                   args.strategy.upper())
     oi = None
@@ -785,8 +850,10 @@ def main():
         print(json.dumps(out), file=JSON_OUT, flush=True)
     if hg is None:
         batch.close()
+        gi.close()
     if dist:
         tdist.destroy_process_group()
+    log("result line written, batch and index released")
 
 
 def bench_c5(args, gi, codes, names, lengths, gname, rank, world, dist, dev, t_index):
@@ -842,9 +909,11 @@ def bench_c5(args, gi, codes, names, lengths, gname, rank, world, dist, dev, t_i
     rank_times = gdist.all_gather_floats(time.perf_counter() - t0)
     dt = max(rank_times)
     value = 2 * pairs * args.steps * world / dt
+    if args.dump_outputs:
+        dump_outputs(batch, args.dump_outputs, np, torch, rank, world)
     st = batch.stats()
     parity = cpu = cpu1 = None
-    if rank == 0:
+    if args.full and rank == 0:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         import oracle as O
         T, tdesc = host_cores()

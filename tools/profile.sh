@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 if [ "$PASS" = all ] || [ "$PASS" = trace ]; then
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats -T --output-format csv -d $OUT/trace -- python3 bench.py $ARGS > $OUT/bench.json 2> $OUT/bench.err || exit $?
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -T --output-format csv -d $OUT/trace -- python3 bench.py --full $ARGS > $OUT/bench.json 2> $OUT/bench.err || exit $?
 fi
 if [ "$PASS" = all ] || [ "$PASS" = pmc ]; then
   LEG="--no-cpu --check 0 --no-pipeline --no-hg19r"

@@ -7,4 +7,4 @@ D=gpurun_out/rehearse
 mkdir -p $D
 timeout -k 10 780 python -u -m pytest tests -m gpu -x -q --timeout 600 --timeout-method thread --durations=15 > $D/tests.log 2>&1 || exit $?
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $D/smoke.log 2>&1 || exit $?
-timeout -k 10 400 python -u bench.py > $D/bench.json 2> $D/bench.err
+timeout -k 10 590 python -u bench.py --full > $D/bench.json 2> $D/bench.err
