@@ -10,7 +10,10 @@
 //
 // The reference formats one record at a time on the host thread that aligned it.  Here one lane
 // formats one read: a length pass (the writer in counting mode), an exclusive scan of the lengths
-// (rocPRIM), and a write pass that puts every read's records at its offset.  The host receives
+// (rocPRIM), and a write pass that puts every read's records at its offset.  In the write pass a
+// lane writes the short fields of its records itself (flag, position, CIGAR, tags) and the workgroup
+// then copies the bulk fields (name, SEQ, QUAL) of all its records together, consecutive lanes on
+// consecutive 16-B chunks (samServeFields).  The host receives
 // the finished text of the batch in one copy, in input order.  A read on which the reference
 // would throw (or whose search failed) is reported through `err` (lowest failing position).
 //
@@ -109,20 +112,25 @@ __global__ void __launch_bounds__(256) encodeLenKernel(const char *__restrict__ 
   lenSeen[m < kLenSeen - 1 ? m : kLenSeen - 1] = 1;
 }
 
-// one read's code row: 16 codes per store (rows are 16-B aligned and zero-padded); a read with
-// spaces in its text (skipped, A/ACGTSequence.java:86-97) takes the byte loop
+// Code rows: kEncLanes consecutive lanes share a read, each converting one 16-B chunk of its text
+// into 16 codes of its row (rows are 16-B aligned and zero-padded), so a wavefront reads the text of
+// 8 neighbouring reads and writes their rows as consecutive 16-B chunks.  A read with spaces in its
+// text (skipped, A/ACGTSequence.java:86-97) takes the byte loop on its first lane.
+constexpr uint32_t kEncLanes = 8;
 __global__ void __launch_bounds__(256) encodeWriteKernel(const char *__restrict__ seq, const uint64_t *__restrict__ seqB,
                                                          const uint64_t *__restrict__ seqE, uint32_t n,
                                                          const uint32_t *__restrict__ codeOff,
                                                          const uint32_t *__restrict__ codeLen,
                                                          uint8_t *__restrict__ codes) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t r = (uint32_t)(tid / kEncLanes), sub = (uint32_t)(tid % kEncLanes);
   if (r >= n) return;
-  uint8_t *o = codes + codeOff[r];
+  const uint32_t o0 = codeOff[r];
+  uint8_t *o = codes + o0;
   const uint64_t b = seqB[r], e = seqE[r];
-  const uint32_t m = codeLen[r], row = codeOff[r + 1] - codeOff[r];
+  const uint32_t m = codeLen[r], row = codeOff[r + 1] - o0;
   if (m == e - b) {
-    for (uint32_t k = 0; k < row; k += 16) {
+    for (uint32_t k = 16 * sub; k < row; k += 16 * kEncLanes) {
       uint32_t w[4];
       load16(seq, b + k, w);
       u32x4 v;
@@ -138,6 +146,7 @@ __global__ void __launch_bounds__(256) encodeWriteKernel(const char *__restrict_
     }
     return;
   }
+  if (sub != 0) return;
   uint32_t k = 0;
   for (uint64_t i = b; i < e; ++i)
     if (seq[i] != ' ') o[k++] = to3bitDev((unsigned char)seq[i]);
@@ -154,7 +163,9 @@ void launchEncode(const char *seq, const uint64_t *seqB, const uint64_t *seqE, u
     size_t b = scanTmpBytes;
     FCHK(rocprim::exclusive_scan(scanTmp, b, rowLen, codeOff, (uint32_t)0, (size_t)n + 1, rocprim::plus<uint32_t>(), s));
   } else {
-    hipLaunchKernelGGL(encodeWriteKernel, grid, dim3(256), 0, s, seq, seqB, seqE, n, codeOff, codeLen, codes);
+    if (n == 0) return;
+    const dim3 g8((unsigned)(((uint64_t)n * kEncLanes + 255) / 256));
+    hipLaunchKernelGGL(encodeWriteKernel, g8, dim3(256), 0, s, seq, seqB, seqE, n, codeOff, codeLen, codes);
     FCHK(hipGetLastError());
   }
 }
@@ -247,41 +258,201 @@ __global__ void __launch_bounds__(256) samLenKernel(SamText t, const OutHeader *
   len[j] = o.n;
 }
 
-// Write pass.  The text of a workgroup's 64 units is one contiguous range of the output
-// [off[j0], off[j0 + 64]); it is formatted into LDS (byte stores that stay on the CU) at the
-// position it has relative to the 16-B aligned start of that range, then copied out with coalesced
-// 16-B stores (the two partial chunks at the range's ends are written bytewise, the neighbouring
-// workgroups own their other bytes).  A range larger than the staging buffer (many reported lines)
-// is written directly to HBM.
-template <int STAGE>
-__global__ void __launch_bounds__(64) samWriteKernel(SamText t, const OutHeader *__restrict__ oh, const OutHit *__restrict__ hits,
+// ---- write pass ----
+
+// bytes [u, u + k) of the 16 bytes W to q[0, k): dword stores where q is 4-B aligned and 4 bytes
+// remain, byte stores otherwise (no store touches a byte outside the range: the neighbouring bytes
+// belong to other lanes)
+__device__ __forceinline__ void putBytes(char *q, const uint32_t (&W)[4], uint32_t u, uint32_t k) {
+  while (k > 0) {
+    const uint32_t d = u >> 2;
+    const uint32_t lo = d == 0 ? W[0] : d == 1 ? W[1] : d == 2 ? W[2] : W[3];
+    const uint32_t hi = d == 0 ? W[1] : d == 1 ? W[2] : d == 2 ? W[3] : 0u;
+    const uint32_t v = __builtin_amdgcn_alignbit(hi, lo, (u & 3) * 8);
+    if ((((uint32_t)(uintptr_t)q) & 3) == 0 && k >= 4) {
+      *reinterpret_cast<uint32_t *>(q) = v;
+      q += 4; u += 4; k -= 4;
+    } else {
+      *q = (char)v;
+      q += 1; u += 1; k -= 1;
+    }
+  }
+}
+
+// 16 bytes of read text or code rows from any address: one unaligned 16-B global load (the text and
+// code allocations are padded, so the 15 bytes after a field's last byte are inside them)
+typedef const __attribute__((address_space(1))) char *GlobalText;
+__device__ __forceinline__ void loadText16(const char *p, uint32_t (&w)[4]) {
+  u32x4 v;
+  __builtin_memcpy(&v, (GlobalText)(uintptr_t)p, 16);
+  w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+}
+
+// SamOut::text of up to 16 bytes: one lane, one 16-B load instead of a load per byte
+__device__ void samSmallCopy(char *dst, const char *src, uint32_t len) {
+  if (len == 0) return;
+  uint32_t w[4];
+  loadText16(src, w);
+  putBytes(dst, w, 0, len);
+}
+
+// A deferred field in the stage: a partial 16-B chunk at its head (up to the first 16-B boundary of
+// the stage), ni whole chunks, a partial chunk at its tail.
+struct SamSpan {
+  const char *src;
+  uint32_t at, len, kind, head, ni;
+};
+__device__ __forceinline__ SamSpan samSpan(const SamField &f) {
+  SamSpan s;
+  s.src = reinterpret_cast<const char *>((uint64_t)f.srcHi << 32 | f.srcLo);
+  s.at = f.w & 0xFFFFu;
+  s.len = (f.w >> 16) & 0x3FFFu;
+  s.kind = f.w >> 30;
+  s.head = (16u - (s.at & 15u)) & 15u;  // (len > 16 > head)
+  s.ni = (s.len - s.head) >> 4;
+  return s;
+}
+// the source of the k output bytes from i0 on (reversed kinds: out[i0 + t] = src[len - 1 - i0 - t])
+__device__ __forceinline__ const char *spanSrc(const SamSpan &s, uint32_t i0, uint32_t k) {
+  return s.kind >= SAM_SEQ_RC ? s.src + (s.len - i0 - k) : s.src + i0;
+}
+// 16 loaded bytes to output bytes: letters for the SEQ kinds; the reversed kinds byte-reversed, so
+// that the k bytes of a partial chunk are then bytes [16 - k, 16)
+__device__ __forceinline__ void spanConvert(uint32_t kind, const uint32_t (&w)[4], uint32_t (&W)[4]) {
+  if (kind >= SAM_SEQ_RC) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      // the complement's letter of codes 0..4 (T G C A N) by byte select
+      const uint32_t x = kind == SAM_SEQ_RC ? __builtin_amdgcn_perm(0x4Eu, 0x41434754u, w[3 - i]) : w[3 - i];
+      W[i] = __builtin_bswap32(x);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)  // SAM_SEQ: the letter of codes 0..4 (A C G T N) by byte select
+      W[i] = kind == SAM_SEQ ? __builtin_amdgcn_perm(0x4Eu, 0x54474341u, w[i]) : w[i];
+  }
+}
+
+// The workgroup's deferred fields, four loads in flight per lane (issued before the first store).
+// Whole chunks: 1 << lshift consecutive lanes share a field, lane `sub` of them takes chunks sub,
+// sub + (1 << lshift), ... (16-B loads of consecutive addresses, aligned 16-B LDS stores).  Then the
+// partial chunks, two per field, one per lane (putBytes).
+__device__ __forceinline__ void samServeFields(const SamField *fields, uint32_t D, char *stage, uint32_t lshift) {
+  const uint32_t L = 1u << lshift, G = blockDim.x >> lshift;
+  const uint32_t sub = threadIdx.x & (L - 1), g = threadIdx.x >> lshift;
+  constexpr int U = 4;
+  for (uint32_t d0 = 0; d0 < D; d0 += G * U) {
+    SamSpan sp[U];
+    uint32_t w[U][4];
+    bool on[U];
+#pragma unroll
+    for (int x = 0; x < U; ++x) {
+      const uint32_t d = d0 + x * G + g;
+      on[x] = false;
+      sp[x].ni = 0;
+      if (d < D) {
+        sp[x] = samSpan(fields[d]);
+        on[x] = sub < sp[x].ni;
+        if (on[x]) loadText16(spanSrc(sp[x], sp[x].head + 16 * sub, 16), w[x]);
+      }
+    }
+#pragma unroll
+    for (int x = 0; x < U; ++x)
+      if (on[x]) {
+        uint32_t W[4];
+        spanConvert(sp[x].kind, w[x], W);
+        u32x4 v;
+        v.x = W[0]; v.y = W[1]; v.z = W[2]; v.w = W[3];
+        *reinterpret_cast<u32x4 *>(stage + sp[x].at + sp[x].head + 16 * sub) = v;
+      }
+#pragma unroll
+    for (int x = 0; x < U; ++x)  // fields of more than L whole chunks
+      for (uint32_t c = sub + L; c < sp[x].ni; c += L) {
+        uint32_t w2[4], W[4];
+        loadText16(spanSrc(sp[x], sp[x].head + 16 * c, 16), w2);
+        spanConvert(sp[x].kind, w2, W);
+        u32x4 v;
+        v.x = W[0]; v.y = W[1]; v.z = W[2]; v.w = W[3];
+        *reinterpret_cast<u32x4 *>(stage + sp[x].at + sp[x].head + 16 * c) = v;
+      }
+  }
+  for (uint32_t e0 = 0; e0 < 2 * D; e0 += blockDim.x * U) {
+    SamSpan sp[U];
+    uint32_t w[U][4], i0[U], k[U];
+#pragma unroll
+    for (int x = 0; x < U; ++x) {
+      const uint32_t e = e0 + blockDim.x * x + threadIdx.x;
+      k[x] = 0;
+      if (e < 2 * D) {
+        sp[x] = samSpan(fields[e >> 1]);
+        i0[x] = e & 1 ? sp[x].head + 16 * sp[x].ni : 0;
+        k[x] = e & 1 ? sp[x].len - i0[x] : sp[x].head;
+        if (k[x]) loadText16(spanSrc(sp[x], i0[x], k[x]), w[x]);
+      }
+    }
+#pragma unroll
+    for (int x = 0; x < U; ++x)
+      if (k[x]) {
+        uint32_t W[4];
+        spanConvert(sp[x].kind, w[x], W);
+        putBytes(stage + sp[x].at + i0[x], W, sp[x].kind >= SAM_SEQ_RC ? 16 - k[x] : 0, k[x]);
+      }
+  }
+}
+
+// units (= lanes) per workgroup of the write pass (128 measured the same: 3.93 against 3.92 ms of
+// gwa_batch_format for 10M 100 bp reads)
+constexpr uint32_t kSamWg = 64;
+
+// Write pass.  The text of a workgroup's units is one contiguous range of the output
+// [off[j0], off[j0 + wg]); it is put together in LDS at the position it has relative to the 16-B
+// aligned start of that range, then copied out with coalesced 16-B stores (the two partial chunks at
+// the range's ends are written bytewise, the neighbouring workgroups own their other bytes).  The
+// stage is filled in two phases: each lane formats its unit, writing the short fields and leaving a
+// descriptor for every bulk field (sam_core.h SamOut::defer; up to `cap` per workgroup, further ones
+// are copied by the lane); after a barrier the workgroup copies the deferred fields
+// (samServeFields).  A range larger than the staging buffer (many reported lines) is written
+// directly to HBM by its lanes.  `out` is only ever written (it may be pinned host memory).
+// Dynamic LDS: cap descriptors of 12 B, the counter, the stage of stageBytes.
+__global__ void __launch_bounds__(kSamWg) samWriteKernel(SamText t, const OutHeader *__restrict__ oh, const OutHit *__restrict__ hits,
                                                      const uint16_t *__restrict__ cig, const uint32_t *__restrict__ idx,
                                                      uint32_t first, uint32_t n, const uint64_t *__restrict__ off,
-                                                     char *__restrict__ out, PairSpec ps) {
-  __shared__ u32x4 stage[STAGE / 16];
-  const uint32_t j0 = blockIdx.x * 64, j = j0 + threadIdx.x;
-  const uint32_t jEnd = j0 + 64 < n ? j0 + 64 : n;
+                                                     char *__restrict__ out, PairSpec ps, uint32_t stageBytes, uint32_t cap,
+                                                     uint32_t lshift) {
+  extern __shared__ u32x4 samLds[];
+  SamField *fields = reinterpret_cast<SamField *>(samLds);
+  const uint32_t descBytes = (cap * (uint32_t)sizeof(SamField) + 4 + 15) & ~15u;
+  uint32_t *count = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(samLds) + descBytes - 4);
+  char *stage = reinterpret_cast<char *>(samLds) + descBytes;
+  const uint32_t j0 = blockIdx.x * blockDim.x, j = j0 + threadIdx.x;
+  const uint32_t jEnd = j0 + blockDim.x < n ? j0 + blockDim.x : n;
   const uint64_t gBeg = off[j0], gEnd = off[jEnd];
   const uint64_t base = gBeg & ~(uint64_t)15;
-  if (gEnd - base > (uint64_t)STAGE) {
+  if (gEnd - base > (uint64_t)stageBytes) {
     if (j < n) {
       SamOut o{out + off[j], 0};
       (void)samUnit(o, t, idx ? idx[j] : first + j, oh, hits, cig, ps);
     }
     return;
   }
+  if (threadIdx.x == 0) *count = 0;
+  __syncthreads();
   if (j < n) {
-    SamOut o{reinterpret_cast<char *>(stage) + (off[j] - base), 0};
+    SamOut o{stage + (off[j] - base), 0, SamDefer{fields, count, cap, stage}};
     (void)samUnit(o, t, idx ? idx[j] : first + j, oh, hits, cig, ps);
   }
   __syncthreads();
+  const uint32_t D = *count < cap ? *count : cap;
+  samServeFields(fields, D, stage, lshift);
+  __syncthreads();
   const uint32_t chunks = (uint32_t)((gEnd - base + 15) >> 4);
-  for (uint32_t c = threadIdx.x; c < chunks; c += 64) {
+  const u32x4 *st = reinterpret_cast<const u32x4 *>(stage);
+  for (uint32_t c = threadIdx.x; c < chunks; c += blockDim.x) {
     const uint64_t a = base + 16ull * c;
     if (a >= gBeg && a + 16 <= gEnd) {
-      *reinterpret_cast<u32x4 *>(out + a) = stage[c];
+      *reinterpret_cast<u32x4 *>(out + a) = st[c];
     } else {
-      const char *sb = reinterpret_cast<const char *>(stage) + 16ull * c;
+      const char *sb = stage + 16ull * c;
       for (int i = 0; i < 16; ++i)
         if (a + i >= gBeg && a + i < gEnd) out[a + i] = sb[i];
     }
@@ -299,28 +470,33 @@ void launchSamFormat(const SamText &t, const OutHeader *oh, const OutHit *hits, 
     FCHK(rocprim::exclusive_scan(scanTmp, *scanTmpBytes, len, off, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
   } else {
     if (n == 0) return;
-    const dim3 g64((n + 63) / 64);
-    // Staging for 64 records: the smallest size that holds 64 records of the batch's average length
-    // with 3 % to spare (a workgroup whose records do not fit writes them directly, correct but
-    // uncoalesced), so more workgroups fit a CU: 20 KiB (8 per CU) for 100 bp, 24 KiB (6) for 150 bp
-    // single-end records; pairs 48 KiB
-    const uint64_t need = n ? totalBytes * 64 * 103 / 100 / n + 16 : 0;
+    const uint32_t wg = kSamWg;
+    const dim3 grid2((n + wg - 1) / wg);
+    // Staging for wg units: what wg units of the batch's average length need with 3 % to spare, in
+    // steps of 256 B (a workgroup whose units do not fit writes them directly, correct but
+    // uncoalesced), so that as many workgroups as possible share a CU's 160 KiB of LDS.
+    // Without a total (totalBytes = 0) 384 B per unit; descriptors and stage together at most 64 KiB.
+    // descriptors: name, SEQ and QUAL of one line per unit (two lines per pair)
+    // (GWA_SAM_DEFER=0, tests and measurements: no descriptors, every lane copies its own fields)
+    const char *dfr = getenv("GWA_SAM_DEFER");
+    const uint32_t lines = ps.np ? 2 : 1, cap = dfr && atoi(dfr) == 0 ? 0 : wg * 3 * lines;
+    const uint32_t descBytes = (cap * (uint32_t)sizeof(SamField) + 4 + 15) & ~15u;
+    const uint64_t stageMax = (65536 - descBytes) & ~255u;  // (and 16 bits of stage offset in a descriptor)
+    uint64_t need = totalBytes ? totalBytes * wg * 103 / 100 / n + 16 : 384 * wg;
+    need = (need + 255) & ~(uint64_t)255;
+    uint32_t stage = (uint32_t)(need < 4096 ? 4096 : need > stageMax ? stageMax : need);
     // GWA_SAM_STAGE (tests): a small staging buffer, so that workgroups whose records do not fit
     // take the direct-write path next to workgroups that stage theirs
     const char *stg = getenv("GWA_SAM_STAGE");
-    if (stg && atoi(stg) > 0) {
-      if (atoi(stg) <= 1024)
-        hipLaunchKernelGGL(samWriteKernel<1024>, g64, dim3(64), 0, s, t, oh, hits, cig, idx, first, n, off, out, ps);
-      else
-        hipLaunchKernelGGL(samWriteKernel<4096>, g64, dim3(64), 0, s, t, oh, hits, cig, idx, first, n, off, out, ps);
-    } else if (ps.np || need > 32768)
-      hipLaunchKernelGGL(samWriteKernel<49152>, g64, dim3(64), 0, s, t, oh, hits, cig, idx, first, n, off, out, ps);
-    else if (need > 24576)
-      hipLaunchKernelGGL(samWriteKernel<32768>, g64, dim3(64), 0, s, t, oh, hits, cig, idx, first, n, off, out, ps);
-    else if (need > 20480 || totalBytes == 0)
-      hipLaunchKernelGGL(samWriteKernel<24576>, g64, dim3(64), 0, s, t, oh, hits, cig, idx, first, n, off, out, ps);
-    else
-      hipLaunchKernelGGL(samWriteKernel<20480>, g64, dim3(64), 0, s, t, oh, hits, cig, idx, first, n, off, out, ps);
+    if (stg && atoi(stg) > 0) stage = atoi(stg) <= 1024 ? 1024 : 4096;
+    // lanes per field from the average field length (a line's SEQ and QUAL are all but ~60 of its bytes)
+    const uint64_t avgLine = totalBytes / n / lines;
+    const uint64_t fieldItems = (avgLine > 64 ? (avgLine - 60) / 2 : 2) / 16;  // whole chunks per field
+    uint32_t lshift = 2;
+    while (lshift < 6 && (1u << lshift) < fieldItems) ++lshift;
+    const uint32_t lds = descBytes + stage;
+    hipLaunchKernelGGL(samWriteKernel, grid2, dim3(wg), lds, s, t, oh, hits, cig, idx, first, n, off, out, ps, stage, cap,
+                       lshift);
     FCHK(hipGetLastError());
   }
 }

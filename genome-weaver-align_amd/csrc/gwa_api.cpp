@@ -298,8 +298,12 @@ struct gwa_batch {
   bool fmtWhole = false;
   unsigned long long *d_stats = nullptr;
   bool statsDone = false;
-  // device encoding of the read text (gwa_batch_run re-encodes every run: the timed path starts
-  // from the text in HBM, as the reference's per-read call starts from the Read's String)
+  // device encoding of the read text (gwa_batch_run writes the code rows from the text every run: the
+  // timed path starts from the text in HBM, as the reference's per-read call starts from the Read's
+  // String).  lenCurrent: d_len / d_row / d_off hold the length pass of the text now in d_seqText
+  // (set by batchTail, which every path that installs a batch's text ends in; a path that changes
+  // the text otherwise must clear it), so a run launches the code-row pass only.
+  bool lenCurrent = false;
   uint32_t *d_row = nullptr, *d_seen = nullptr;
   void *d_encTmp = nullptr;
   size_t encTmpBytes = 0;
@@ -752,6 +756,7 @@ static void batchTail(gwa_batch *b, uint64_t seqBytes) {
                b->encTmpBytes, 0, s);
   HIPCHK(hipMemcpyAsync(seen.data(), b->d_seen, kLenSeen * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
+  b->lenCurrent = true;
   // the distinct read lengths: maximum length, k per length (AlignmentScoreConfig
   // .getMaximumEditDistance) and the staircase tables
   std::vector<int> lens;
@@ -1067,11 +1072,14 @@ int gwa_batch_run(gwa_batch_t *b) {
     Scratch scr(ix, s);  // this run's search scratch (from the index's pool, back to it at the end)
     Events ev;
     hipEvent_t e0 = ev.e[0], e1 = ev.e[1], e2 = ev.e[2];
-    // encode the read text in HBM (ACGTSequence(String), A/ACGTSequence.java:86-97): lengths and
-    // code offsets, then the code rows
+    // encode the read text in HBM (ACGTSequence(String), A/ACGTSequence.java:86-97): the code rows, at
+    // the lengths and code offsets batchTail computed from this text
     HIPCHK(hipEventRecord(e2, s));
-    launchEncode(b->d_seqText, b->d_seqB, b->d_seqE, b->n, b->d_len, b->d_row, b->d_off, b->d_seen, b->d_codes,
-                 b->d_encTmp, b->encTmpBytes, 0, s);
+    if (!b->lenCurrent) {
+      launchEncode(b->d_seqText, b->d_seqB, b->d_seqE, b->n, b->d_len, b->d_row, b->d_off, b->d_seen, b->d_codes,
+                   b->d_encTmp, b->encTmpBytes, 0, s);
+      b->lenCurrent = true;
+    }
     launchEncode(b->d_seqText, b->d_seqB, b->d_seqE, b->n, b->d_len, b->d_row, b->d_off, b->d_seen, b->d_codes,
                  b->d_encTmp, b->encTmpBytes, 1, s);
     HIPCHK(hipMemsetAsync(b->d_count, 0, 16 * sizeof(uint32_t), s));

@@ -4,8 +4,14 @@
 //   SAMOutput.emit            (A/SAMOutput.java:73-82)
 // The same function measures a record (SamOut with p == nullptr counts bytes) and writes it, so the
 // device formats a batch in two passes: lengths, an exclusive scan, then every read's text at its
-// offset (sam_format.hip).  SAM flag values follow the SAM spec (utgb SAMReadFlag is unvendored;
+// offset (batch_io.hip).  SAM flag values follow the SAM spec (utgb SAMReadFlag is unvendored;
 // SURVEY.md §8c).
+//
+// The bulk fields of a line (read name, SEQ, QUAL) go through SamOut::text / seq / qual.  On the host
+// and in counting mode they are copied (or counted) at once.  In the device write pass a lane only
+// advances its cursor over a bulk field of more than kSamDeferMin bytes and leaves a SamField
+// descriptor in LDS; the workgroup then copies all deferred fields together with coalesced 16-B
+// loads (batch_io.hip samServeFields).  Everything else is written by the lane itself.
 #pragma once
 #include "gwa_layout.h"
 
@@ -28,17 +34,58 @@ struct SamText {
   int32_t starKey, emptyKey; // the keys of the names "*" and "" (a contig may be called that)
 };
 
+// A bulk field left to the workgroup (device write pass): out[i] = f(src[i]), or, for the reversed
+// kinds, out[i] = f(src[len - 1 - i]), at byte `at` of the workgroup's staging buffer.
+enum : uint32_t {
+  SAM_COPY = 0,    // bytes as they are
+  SAM_SEQ = 1,     // codes 0..4 -> ACGTN
+  SAM_SEQ_RC = 2,  // reversed, codes -> the complement's letter
+  SAM_REV = 3      // reversed bytes
+};
+constexpr uint32_t kSamDeferMin = 16;       // longer fields are deferred, shorter ones copied by the lane
+constexpr uint32_t kSamDeferMax = 1 << 14;  // (14 bits of length in a descriptor)
+struct SamField {
+  uint32_t srcLo, srcHi;  // source address
+  uint32_t w;             // at | len << 16 | kind << 30
+};
+struct SamDefer {
+  SamField *f = nullptr;      // descriptor list (LDS); nullptr: nothing is deferred
+  uint32_t *count = nullptr;  // fields pushed so far (may exceed cap: those were copied at once)
+  uint32_t cap = 0;
+  char *stage = nullptr;      // the staging buffer `at` is relative to
+};
+#if defined(__HIP_DEVICE_COMPILE__)
+// up to 16 bytes of read text copied by one lane (batch_io.hip)
+__device__ void samSmallCopy(char *dst, const char *src, uint32_t len);
+#endif
+
 // byte sink: counts when p == nullptr
 struct SamOut {
   char *p;
   uint64_t n;
+  SamDefer d{};  // device write pass: where bulk fields are deferred to
   GWA_HD void ch(char c) {
     if (p) p[n] = c;
     ++n;
   }
-  // Text copies run 16 bytes per pass with the 16 loads issued before any store: a record's name,
-  // sequence and quality (~250 B) then wait on memory ~16 times, not once per byte (the SAM writer is
-  // latency-bound: a few workgroups per CU, each lane formatting one record)
+  // true: the field [p + n, p + n + len) was left to the workgroup and the cursor moved past it
+  GWA_HD bool defer(const void *src, uint64_t len, uint32_t kind) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (d.f && len > kSamDeferMin && len < kSamDeferMax) {
+      const uint32_t slot = atomicAdd(d.count, 1u);
+      if (slot < d.cap) {
+        const uint64_t a = (uint64_t)src;
+        d.f[slot] = SamField{(uint32_t)a, (uint32_t)(a >> 32),
+                             (uint32_t)(p + n - d.stage) | (uint32_t)len << 16 | kind << 30};
+        n += len;
+        return true;
+      }
+    }
+#endif
+    return false;
+  }
+  // Text copies run 16 bytes per pass with the 16 loads issued before any store (short fields, contig
+  // names and literals on the device; every field on the host)
   GWA_HD void bytes(const char *s, uint64_t len) {
     if (p) {
       for (uint64_t i = 0; i < len; i += 16) {
@@ -52,6 +99,22 @@ struct SamOut {
     }
     n += len;
   }
+  // read text (a name, a forward quality): s lies in a text allocation padded for 16-B chunk loads
+  GWA_HD void text(const char *s, uint64_t len) {
+    if (defer(s, len, SAM_COPY)) return;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (p && len <= 16) {
+      samSmallCopy(p + n, s, (uint32_t)len);
+      n += len;
+      return;
+    }
+#endif
+    bytes(s, len);
+  }
+  // SEQ: positions [a, b) of the read c[0, m) as letters; rc: of its reverse complement
+  GWA_HD void seq(const uint8_t *c, int m, int a, int b, bool rc);
+  // QUAL: positions [a, b) of the quality q[0, qn); rev: of the reversed quality
+  GWA_HD void qual(const char *q, uint64_t qn, int a, int b, bool rev);
   template <unsigned long L>
   GWA_HD void lit(const char (&s)[L]) {  // a string literal (without its terminating 0)
     bytes(s, L - 1);
@@ -88,6 +151,50 @@ constexpr char kSym[5] = {'A', 'C', 'G', 'T', 'N'};
 // kSym[x] as a shift of one packed constant (a table lookup is a memory load per base on the device)
 GWA_HD char sym(unsigned x) { return (char)((0x4E54474341ULL >> (8 * x)) & 0xFF); }
 constexpr char kOp[8] = {'M', 'I', 'D', 'N', 'S', 'H', 'P', 'X'};
+}  // namespace samfmt
+
+// (16 positions per pass, loads first: SamOut::bytes)
+GWA_HD void SamOut::seq(const uint8_t *c, int m, int a, int b, bool rc) {
+  if (b <= a) return;
+  if (!p) {
+    n += (uint64_t)(b - a);
+    return;
+  }
+  if (defer(rc ? c + (m - b) : c + a, (uint64_t)(b - a), rc ? SAM_SEQ_RC : SAM_SEQ)) return;
+  for (int j0 = a; j0 < b; j0 += 16) {
+    uint8_t x[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int j = j0 + k;
+      x[k] = j < b ? (rc ? c[m - 1 - j] : c[j]) : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (j0 + k < b) ch(samfmt::sym(rc ? (x[k] < 4 ? 3 - x[k] : 4) : (x[k] > 4 ? 4 : x[k])));
+  }
+}
+
+GWA_HD void SamOut::qual(const char *q, uint64_t qn, int a, int b, bool rev) {
+  if (b <= a) return;
+  if (!p) {
+    n += (uint64_t)(b - a);
+    return;
+  }
+  if (defer(rev ? q + (qn - (uint64_t)b) : q + a, (uint64_t)(b - a), rev ? SAM_REV : SAM_COPY)) return;
+  for (int j0 = a; j0 < b; j0 += 16) {
+    char x[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int j = j0 + k;
+      x[k] = j < b ? (rev ? q[qn - 1 - j] : q[j]) : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (j0 + k < b) ch(x[k]);
+  }
+}
+
+namespace samfmt {
 
 GWA_HD char stateCh(int numHits) { return numHits > 0 ? (numHits == 1 ? 'U' : 'R') : 'N'; }
 
@@ -169,20 +276,8 @@ GWA_HD void chrName(SamOut &o, Ctx &cx, int chr) {
   } else cx.npe = true;  // null chr
 }
 
-// (16 positions per pass, loads first: SamOut::bytes)
 GWA_HD void emitSeq(SamOut &o, const Ctx &cx, int a, int b) {
-  const uint8_t *c = cx.t.codes + cx.t.codeOff[cx.r];
-  for (int j0 = a; j0 < b; j0 += 16) {
-    uint8_t x[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const int j = j0 + k;
-      x[k] = j < b ? (cx.strand == 0 ? c[j] : c[cx.m - 1 - j]) : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (j0 + k < b) o.ch(sym(cx.strand == 0 ? x[k] : (x[k] < 4 ? 3 - x[k] : 4)));
-  }
+  o.seq(cx.t.codes + cx.t.codeOff[cx.r], cx.m, a, b, cx.strand != 0);
 }
 
 GWA_HD void emitQual(SamOut &o, const Ctx &cx, int a, int b) {
@@ -190,18 +285,7 @@ GWA_HD void emitQual(SamOut &o, const Ctx &cx, int a, int b) {
     o.ch('*');
     return;
   }
-  const char *q = cx.t.qual + cx.q0;
-  for (int j0 = a; j0 < b; j0 += 16) {
-    char x[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const int j = j0 + k;
-      x[k] = j < b ? (cx.strand == 0 ? q[j] : q[cx.qn - 1 - j]) : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (j0 + k < b) o.ch(x[k]);
-  }
+  o.qual(cx.t.qual + cx.q0, cx.qn, a, b, cx.strand != 0);
 }
 
 GWA_HD void emitState(SamOut &o, const Ctx &cx, int head, int self) {
@@ -226,7 +310,7 @@ GWA_HD bool lineOne(SamOut &o, Ctx &cx, const Rec &r, const Rec *split, bool has
   if (eachMapped) flag |= 0x2;
   if (r.numBestHits <= 0) flag |= 0x4;
   if (split && split->numBestHits <= 0) flag |= 0x8;
-  o.bytes(cx.t.name + cx.t.nameB[cx.r], cx.t.nameE[cx.r] - cx.t.nameB[cx.r]);
+  o.text(cx.t.name + cx.t.nameB[cx.r], cx.t.nameE[cx.r] - cx.t.nameB[cx.r]);
   o.ch('\t');
   o.num(flag);
   o.ch('\t');
@@ -365,20 +449,11 @@ GWA_HD int samChain(SamOut &o, const SamText &t, uint32_t r, const OutHit *hits,
 // The unmapped record: ReadHit("*", 0, 0, 0, 0, -1, FORWARD, CIGAR(), 0)
 // (S/BidirectionalSuffixFilter.java:258-261)
 GWA_HD void samUnmapped(SamOut &o, const SamText &t, uint32_t r) {
-  o.bytes(t.name + t.nameB[r], t.nameE[r] - t.nameB[r]);
+  o.text(t.name + t.nameB[r], t.nameE[r] - t.nameB[r]);
   o.lit("\t68\t*\t0\t1\t\t*\t0\t0\t");
-  const uint8_t *c = t.codes + t.codeOff[r];
-  const uint32_t len = t.codeLen[r];
-  for (uint32_t j0 = 0; j0 < len; j0 += 16) {
-    uint8_t x[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) x[k] = j0 + k < len ? c[j0 + k] : 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (j0 + k < len) o.ch(samfmt::sym(x[k] > 4 ? 4 : x[k]));
-  }
+  o.seq(t.codes + t.codeOff[r], (int)t.codeLen[r], 0, (int)t.codeLen[r], false);
   o.ch('\t');
-  if (!qualAbsent(t, r)) o.bytes(t.qual + t.qualB[r], t.qualE[r] - t.qualB[r]);
+  if (!qualAbsent(t, r)) o.text(t.qual + t.qualB[r], t.qualE[r] - t.qualB[r]);
   else o.ch('*');
   o.ch('\n');
 }
@@ -427,7 +502,7 @@ GWA_HD void samMateLine(SamOut &o, const SamText &t, uint32_t r, const OutHit *h
   if (!mate) flag |= 0x8;
   if (h && h->strand == 1) flag |= 0x10;
   if (mate && mate->strand == 1) flag |= 0x20;
-  o.bytes(t.name + t.nameB[r], t.nameE[r] - t.nameB[r]);
+  o.text(t.name + t.nameB[r], t.nameE[r] - t.nameB[r]);
   o.ch('\t');
   o.num(flag);
   o.ch('\t');
@@ -456,18 +531,14 @@ GWA_HD void samMateLine(SamOut &o, const SamText &t, uint32_t r, const OutHit *h
   o.num(h && mate && sameChr ? (leftmost ? tlenAbs : -tlenAbs) : 0);
   o.ch('\t');
   const bool rev = h && h->strand == 1;
-  const uint8_t *c = t.codes + t.codeOff[r];
   const int m = (int)t.codeLen[r];
-  for (int j = 0; j < m; ++j) {
-    const uint8_t x = rev ? c[m - 1 - j] : c[j];
-    o.ch(samfmt::sym(!rev ? (x > 4 ? 4 : x) : (x < 4 ? 3 - x : 4)));
-  }
+  o.seq(t.codes + t.codeOff[r], m, 0, m, rev);
   o.ch('\t');
   if (qualAbsent(t, r)) {
     o.ch('*');
   } else {
-    const uint64_t q0 = t.qualB[r], qn = t.qualE[r] - t.qualB[r];
-    for (uint64_t j = 0; j < qn; ++j) o.ch(rev ? t.qual[q0 + qn - 1 - j] : t.qual[q0 + j]);
+    const uint64_t qn = t.qualE[r] - t.qualB[r];
+    o.qual(t.qual + t.qualB[r], qn, 0, (int)qn, rev);
   }
   if (h) {
     o.lit("\tNM:i:");
