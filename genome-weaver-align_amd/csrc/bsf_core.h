@@ -107,59 +107,92 @@ GWA_HD T pick(const T (&a)[N], int i) {
 // Rank on one 64-B Occ block (A/OccurrenceCountTable.java:80-107, A/ACGTSequence.java:456-549)
 // ---------------------------------------------------------------------------------------------
 struct Block {
-  uint32_t cnt[4];
-  uint64_t lo0, lo1, hi0, hi1, n0, n1;
+  uint32_t cnt[4];   // counts of A,C,G,T up to the block's middle (cnt[0]: with the has-N bit until finishBlock)
+  uint64_t lo, hi;   // the planes of the half that holds offset i & 127
+  uint64_t n;        // that half's N bitmap
 };
 
-GWA_HD void loadBlock(const OccBlock *occ, uint64_t b, Block &o) {
+// Requests what a rank at position i needs of its block: the counts and the half of i, two 16-B
+// loads (and, in the plain mode, the N word of that half).  Nothing loaded is looked at here, so a
+// caller may put other work between this and finishBlock.
+GWA_HD void loadBlock(const OccBlock *occ, uint64_t i, int mode, Block &o) {
+  const uint32_t half = (uint32_t)(i >> 6) & 1u;
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 *p = reinterpret_cast<const u32x4 *>(occ + b);
+  const u32x4 *p = reinterpret_cast<const u32x4 *>(occ + (i >> 7));
   u32x4 a = __builtin_nontemporal_load(p + 0);
-  u32x4 l = __builtin_nontemporal_load(p + 1);
-  u32x4 h = __builtin_nontemporal_load(p + 2);
-  u32x4 n = __builtin_nontemporal_load(p + 3);
+  u32x4 h = __builtin_nontemporal_load(p + 1 + half);
+  o.n = 0;
+  if (mode != kOccFlagged) o.n = __builtin_nontemporal_load(reinterpret_cast<const uint64_t *>(p + 3) + half);
   o.cnt[0] = a.x; o.cnt[1] = a.y; o.cnt[2] = a.z; o.cnt[3] = a.w;
-  o.lo0 = ((uint64_t)l.y << 32) | l.x; o.lo1 = ((uint64_t)l.w << 32) | l.z;
-  o.hi0 = ((uint64_t)h.y << 32) | h.x; o.hi1 = ((uint64_t)h.w << 32) | h.z;
-  o.n0 = ((uint64_t)n.y << 32) | n.x; o.n1 = ((uint64_t)n.w << 32) | n.z;
+  o.lo = ((uint64_t)h.y << 32) | h.x; o.hi = ((uint64_t)h.w << 32) | h.z;
 #else
-  const OccBlock &B = occ[b];
-  for (int i = 0; i < 4; ++i) o.cnt[i] = B.cnt[i];
-  o.lo0 = B.lo[0]; o.lo1 = B.lo[1]; o.hi0 = B.hi[0]; o.hi1 = B.hi[1]; o.n0 = B.nmask[0]; o.n1 = B.nmask[1];
+  const OccBlock &B = occ[i >> 7];
+  for (int c = 0; c < 4; ++c) o.cnt[c] = B.cnt[c];
+  o.lo = half ? B.h1[0] : B.h0[0];
+  o.hi = half ? B.h1[1] : B.h0[1];
+  o.n = mode != kOccFlagged ? B.nmask[half] : 0;
 #endif
 }
+// Flagged mode: takes the has-N bit out of the counts and, for the rare block that holds an N,
+// reads the N word of i's half (a third load, behind a divergent branch).  Eager mode: only takes
+// the bit out (loadBlock has read the N word).  Plain mode: nothing.
+GWA_HD void finishBlock(const OccBlock *occ, uint64_t i, int mode, Block &o) {
+  if (mode == kOccPlain) return;
+  const bool hasN = (o.cnt[0] & kOccHasN) != 0;
+  o.cnt[0] &= ~kOccHasN;
+  if (mode == kOccFlagged && hasN) {
+    const uint64_t *q = occ[i >> 7].nmask + ((i >> 6) & 1);
+#if defined(__HIP_DEVICE_COMPILE__)
+    o.n = __builtin_nontemporal_load(q);
+#else
+    o.n = *q;
+#endif
+  }
+}
 
-// counts of A,C,G,T,N in bwt[0, i) where i lies in block B (i>>7 == block index)
-GWA_HD void rankAll(const Block &B, uint64_t i, uint64_t out[5]) {
+// The codes a rank at offset r = i & 127 counts: [64, r) of half 1, added to the midpoint counts
+// (up), or [r, 64) of half 0, taken off them
+struct RankSpan {
+  uint64_t m;     // their bits in the half's words
+  uint32_t span;  // how many
+  bool up;
+};
+GWA_HD RankSpan rankSpan(uint64_t i) {
   const uint32_t r = (uint32_t)(i & 127);
-  const uint64_t m0 = r >= 64 ? ~0ULL : ((1ULL << r) - 1ULL);
-  const uint64_t m1 = r > 64 ? ((1ULL << (r - 64)) - 1ULL) : 0ULL;
-  const uint32_t pLo = popc64(B.lo0 & m0) + popc64(B.lo1 & m1);
-  const uint32_t pHi = popc64(B.hi0 & m0) + popc64(B.hi1 & m1);
-  const uint32_t pT = popc64(B.lo0 & B.hi0 & m0) + popc64(B.lo1 & B.hi1 & m1);
-  const uint32_t pN = popc64(B.n0 & m0) + popc64(B.n1 & m1);
+  RankSpan s;
+  s.up = r >= 64;
+  s.m = s.up ? ((1ULL << (r - 64)) - 1ULL) : ~((1ULL << r) - 1ULL);
+  s.span = s.up ? r - 64 : 64 - r;
+  return s;
+}
+GWA_HD uint64_t rankApply(const RankSpan &s, uint32_t cnt, uint32_t x) {
+  return s.up ? (uint64_t)cnt + x : (uint64_t)cnt - x;
+}
+
+// counts of A,C,G,T,N in bwt[0, i) where B = the block of i (loadBlock + finishBlock at i), i <= N
+GWA_HD void rankAll(const Block &B, uint64_t i, uint64_t out[5]) {
+  const RankSpan s = rankSpan(i);
+  const uint32_t pLo = popc64(B.lo & s.m);
+  const uint32_t pHi = popc64(B.hi & s.m);
+  const uint32_t pT = popc64(B.lo & B.hi & s.m);
+  const uint32_t pN = popc64(B.n & s.m);
   const uint32_t cC = pLo - pT, cG = pHi - pT;
-  const uint32_t cA = r - cC - cG - pT - pN;
-  out[0] = (uint64_t)B.cnt[0] + cA;
-  out[1] = (uint64_t)B.cnt[1] + cC;
-  out[2] = (uint64_t)B.cnt[2] + cG;
-  out[3] = (uint64_t)B.cnt[3] + pT;
+  const uint32_t cA = s.span - cC - cG - pT - pN;
+  out[0] = rankApply(s, B.cnt[0], cA);
+  out[1] = rankApply(s, B.cnt[1], cC);
+  out[2] = rankApply(s, B.cnt[2], cG);
+  out[3] = rankApply(s, B.cnt[3], pT);
   out[4] = i - out[0] - out[1] - out[2] - out[3];
 }
 
 GWA_HD uint64_t rankOne(const Block &B, uint64_t i, int ch) {
-  const uint32_t r = (uint32_t)(i & 127);
-  const uint64_t m0 = r >= 64 ? ~0ULL : ((1ULL << r) - 1ULL);
-  const uint64_t m1 = r > 64 ? ((1ULL << (r - 64)) - 1ULL) : 0ULL;
+  const RankSpan s = rankSpan(i);
   switch (ch) {
-    case 1: return (uint64_t)B.cnt[1] + popc64(B.lo0 & ~B.hi0 & m0) + popc64(B.lo1 & ~B.hi1 & m1);
-    case 2: return (uint64_t)B.cnt[2] + popc64(B.hi0 & ~B.lo0 & m0) + popc64(B.hi1 & ~B.lo1 & m1);
-    case 3: return (uint64_t)B.cnt[3] + popc64(B.hi0 & B.lo0 & m0) + popc64(B.hi1 & B.lo1 & m1);
-    case 0: {
-      uint32_t any = popc64((B.lo0 | B.hi0 | B.n0) & m0) + popc64((B.lo1 | B.hi1 | B.n1) & m1);
-      return (uint64_t)B.cnt[0] + (r - any);
-    }
+    case 1: return rankApply(s, B.cnt[1], popc64(B.lo & ~B.hi & s.m));
+    case 2: return rankApply(s, B.cnt[2], popc64(B.hi & ~B.lo & s.m));
+    case 3: return rankApply(s, B.cnt[3], popc64(B.hi & B.lo & s.m));
+    case 0: return rankApply(s, B.cnt[0], s.span - popc64((B.lo | B.hi | B.n) & s.m));
     default: {
       uint64_t o[5];
       rankAll(B, i, o);
@@ -171,13 +204,19 @@ GWA_HD uint64_t rankOne(const Block &B, uint64_t i, int ch) {
 // One entry of the k-mer interval table (IndexView::kmer): K backward-search steps
 // (A/FMIndexOnOccTable.java:47-51) from [0, N) over `key`, first-processed base in the low bits
 // (the order of the 2-bit packed read words, so a key is a shifted window of them).
+// Works on an index of either Occ mode without being told which: it always reads the N word (the
+// plain mode's loads), and clears the has-N bit whenever the counts leave it free (occCountsFit),
+// where a plain index has it clear anyway.  (Built once per index: the third load does not matter.)
 GWA_HD uint64_t kmerInterval(const OccBlock *occ, const uint64_t C[5], uint64_t N, uint32_t key, int K) {
+  const uint32_t keep = occCountsFit(C) ? ~kOccHasN : ~0u;
   uint64_t lb = 0, ub = N;
   for (int j = 0; j < K; ++j) {
     const int ch = (int)((key >> (2 * j)) & 3);
     Block B0, B1;
-    loadBlock(occ, lb >> 7, B0);
-    loadBlock(occ, ub >> 7, B1);
+    loadBlock(occ, lb, kOccPlain, B0);
+    loadBlock(occ, ub, kOccPlain, B1);
+    B0.cnt[0] &= keep;
+    B1.cnt[0] &= keep;
     const uint64_t nlb = C[ch] + rankOne(B0, lb, ch), nub = C[ch] + rankOne(B1, ub, ch);
     if (nlb >= nub) return 0;
     lb = nlb;
@@ -508,7 +547,8 @@ struct BsfLane {
   GWA_HD uint64_t occOne(int fm, int ch, uint64_t i) {
     if (i > ix.N) i = ix.N;
     Block B;
-    loadBlock(ix.occ[fm], i >> 7, B);
+    loadBlock(ix.occ[fm], i, ix.occMode, B);
+    finishBlock(ix.occ[fm], i, ix.occMode, B);
     ++blocks;
     return rankOne(B, i, ch);
   }
@@ -518,9 +558,15 @@ struct BsfLane {
     if (ub > ix.N) ub = ix.N;
     // both blocks are requested before either is used: one memory round trip, not two
     const int two = (ub >> 7) != (lb >> 7);
+    // (the -m sf step's rank, its only caller: the N words are read eagerly, three loads per block
+    // in one straight line and no branch on the has-N bit inside sfStepT's children loop, whose
+    // divergent control flow gfx950 has miscompiled before -- DESIGN.md §7)
+    const int md = occEager(ix.occMode);
     Block B0, B1;
-    loadBlock(ix.occ[fm], lb >> 7, B0);
-    loadBlock(ix.occ[fm], ub >> 7, B1);  // same line when !two (an L2 hit)
+    loadBlock(ix.occ[fm], lb, md, B0);
+    loadBlock(ix.occ[fm], ub, md, B1);  // same line when !two (an L2 hit)
+    finishBlock(ix.occ[fm], lb, md, B0);
+    finishBlock(ix.occ[fm], ub, md, B1);
     blocks += 1 + two;
     rankAll(B0, lb, lo);
     rankAll(B1, ub, hi);
@@ -1232,14 +1278,16 @@ struct BsfLane {
     } else {
       const int ch = q(strand, i);
       // backwardSearch(ch, si) = C[ch] + getOcc(ch, lb|ub) (A/FMIndexOnOccTable.java:47-51);
-      // one 64-B block when lb and ub share a 128-position window
+      // one 64-B block when lb and ub share a 128-position window, one half of it when they share that
       Block B;
-      loadBlock(ix.occ[fm], s.lb >> 7, B);
+      loadBlock(ix.occ[fm], s.lb, ix.occMode, B);
+      finishBlock(ix.occ[fm], s.lb, ix.occMode, B);
       ++blocks;
       nlb = ix.C[ch] + rankOne(B, s.lb, ch);
-      if ((s.ub >> 7) != (s.lb >> 7)) {
-        loadBlock(ix.occ[fm], s.ub >> 7, B);
-        ++blocks;
+      if ((s.ub >> 6) != (s.lb >> 6)) {
+        loadBlock(ix.occ[fm], s.ub, ix.occMode, B);
+        finishBlock(ix.occ[fm], s.ub, ix.occMode, B);
+        blocks += (s.ub >> 7) != (s.lb >> 7) ? 1 : 0;
       }
       nub = ix.C[ch] + rankOne(B, s.ub, ch);
       ++quickSteps;
@@ -1994,8 +2042,8 @@ struct BsfLane {
       if (b != tcWN) { tcCN = ix.textN[b]; tcWN = b; }
     }
     if (kind == K_RANK) {
-      loadBlock(ix.occ[fmR], rl >> 7, B0);
-      loadBlock(ix.occ[fmR], ru >> 7, B1);  // same line when both share a window (an L2 hit)
+      loadBlock(ix.occ[fmR], rl, ix.occMode, B0);
+      loadBlock(ix.occ[fmR], ru, ix.occMode, B1);  // same line when both share a window (an L2 hit)
       blocks += 1 + ((ru >> 7) != (rl >> 7) ? 1 : 0);
     }
     between();
@@ -2012,6 +2060,9 @@ struct BsfLane {
     }
     if (kind == K_RANK) {
       uint64_t lo[5], hi[5];
+      // (flagged mode: the N word of the rare block that holds an N is read here, after `between`)
+      finishBlock(ix.occ[fmR], rl, ix.occMode, B0);
+      finishBlock(ix.occ[fmR], ru, ix.occMode, B1);
       rankAll(B0, rl, lo);
       rankAll(B1, ru, hi);
       for (int i = 0; i < 4; ++i) {

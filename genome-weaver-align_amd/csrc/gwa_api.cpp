@@ -356,7 +356,7 @@ static void freeIndexDev(gwa_index *ix) {
 namespace gwa {
 bool cyclicSAGpu(const uint8_t *d_T, uint64_t N, uint32_t *d_sa, int alphabetBits, hipStream_t s);
 void reverseTextGpu(const uint8_t *d_T, uint64_t N, uint8_t *d_R, hipStream_t s);
-void buildOccGpu(const uint8_t *d_T, const uint32_t *d_sa, uint64_t N, OccBlock *d_occ, hipStream_t s);
+void buildOccGpu(const uint8_t *d_T, const uint32_t *d_sa, uint64_t N, int occMode, OccBlock *d_occ, hipStream_t s);
 void packTextGpu(const uint8_t *d_T, uint64_t N, uint64_t *d_text2, uint64_t *d_textN, hipStream_t s);
 void unpackTextGpu(const uint64_t *d_text2, const uint64_t *d_textN, uint64_t N, uint8_t *d_T, hipStream_t s);
 void countCodesGpu(const uint8_t *d_T, uint64_t N, unsigned long long *d_cnt5, hipStream_t s);
@@ -372,6 +372,19 @@ static void buildFromDeviceText(gwa_index *ix, uint8_t *dT) {
   const uint64_t N = h.N;
   uint8_t *dR = nullptr;
   try {
+    // CharacterCount.C (A/CharacterCount.java:41-50)
+    unsigned long long *dCnt = devAlloc<unsigned long long>(5);
+    countCodesGpu(dT, N, dCnt, s);
+    unsigned long long count[5];
+    HIPCHK(hipMemcpyAsync(count, dCnt, sizeof(count), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    (void)hipFree(dCnt);
+    uint64_t sum = 0;
+    for (int c = 0; c < 5; ++c) { h.C[c] = sum; sum += count[c]; }
+    // the Occ blocks' mode (OccBlock, gwa_layout.h): the has-N flag where the counts leave its bit
+    // free; GWA_OCC_PLAIN=1 builds the unflagged layout regardless (tests)
+    const char *plain = getenv("GWA_OCC_PLAIN");
+    h.occMode = (plain && atoi(plain)) || !occCountsFit(h.C) ? kOccPlain : kOccFlagged;
     dR = devAlloc<uint8_t>(N);
     reverseTextGpu(dT, N, dR, s);
     ix->d_sa[0] = devAlloc<uint32_t>(N, &ix->bytes);
@@ -382,23 +395,14 @@ static void buildFromDeviceText(gwa_index *ix, uint8_t *dT) {
     const uint64_t nb = N / 128 + 1;
     ix->d_occ[0] = devAlloc<OccBlock>(nb, &ix->bytes);
     ix->d_occ[1] = devAlloc<OccBlock>(nb, &ix->bytes);
-    buildOccGpu(dT, ix->d_sa[0], N, ix->d_occ[0], s);
-    buildOccGpu(dR, ix->d_sa[1], N, ix->d_occ[1], s);
+    buildOccGpu(dT, ix->d_sa[0], N, h.occMode, ix->d_occ[0], s);
+    buildOccGpu(dR, ix->d_sa[1], N, h.occMode, ix->d_occ[1], s);
     if (!ix->d_text2) {
       const uint64_t nw = N / 64 + 1;
       ix->d_text2 = devAlloc<uint64_t>(2 * nw, &ix->bytes);
       ix->d_textN = devAlloc<uint64_t>(nw, &ix->bytes);
       packTextGpu(dT, N, ix->d_text2, ix->d_textN, s);
     }
-    // CharacterCount.C (A/CharacterCount.java:41-50)
-    unsigned long long *dCnt = devAlloc<unsigned long long>(5);
-    countCodesGpu(dT, N, dCnt, s);
-    unsigned long long count[5];
-    HIPCHK(hipMemcpyAsync(count, dCnt, sizeof(count), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    (void)hipFree(dCnt);
-    uint64_t sum = 0;
-    for (int c = 0; c < 5; ++c) { h.C[c] = sum; sum += count[c]; }
   } catch (...) {
     (void)hipFree(dT);
     if (dR) (void)hipFree(dR);
@@ -426,6 +430,7 @@ static void buildFromDeviceText(gwa_index *ix, uint8_t *dT) {
   v.contigOff = ix->d_contig;
   v.nContig = (int32_t)h.names.size();
   v.N = N;
+  v.occMode = h.occMode;
   for (int c = 0; c < 5; ++c) v.C[c] = h.C[c];
   // k-mer interval tables for FMQuickScan restarts (IndexView::kmer)
   v.kmerK = kmerKFor(N);

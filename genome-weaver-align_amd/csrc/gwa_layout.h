@@ -23,18 +23,40 @@
 
 namespace gwa {
 
-// One Occ block: counts of A,C,G,T in bwt[0, 128*b), then the 128 codes of the block as two
-// bit planes (lo = code&1, hi = code>>1; position p at bit p%64 of word p/64) and the N bitmap.
-// N positions carry code 0 in the planes; occ(A) subtracts them, occ(N) = i - sum(ACGT).
+// One Occ block, four 16-B quarters: the counts of A,C,G,T in bwt[0, 128*b + 64), i.e. up to the
+// block's MIDDLE; the 64 codes of each half as two bit planes (lo = code&1, hi = code>>1; position
+// p at bit p%64 of half p/64); the N bitmap of both halves.  N positions carry code 0 in the planes;
+// occ(A) subtracts them, occ(N) = i - sum(ACGT).  A rank at offset r = i & 127 reads the counts and
+// ONE half (two 16-B loads, bsf_core.h loadBlock): the counts minus the codes in [r, 64) of half 0
+// for r < 64, the counts plus the codes in [64, r) of half 1 otherwise.  Positions >= N of the last
+// block read as code 0 in the planes and are counted as A in its cnt[0], so the subtraction (which
+// always spans them: i <= N) takes them out again.
+// The N quarter is needed only where a half holds an N, which almost no BWT block does: in the
+// flagged mode (kOccFlagged) bit 31 of cnt[0] says that the block holds one, and only then is the
+// quarter read.  That bit is free while every count stays below 2^31 (occCountsFit); an index whose
+// counts do not fit is built in the plain mode (kOccPlain: no flag, every rank reads the quarter).
 // Reproduces OccurrenceCountTable.getOcc/getOccACGTN (A/OccurrenceCountTable.java:80-107)
 // with W = 128 (A/FMIndexOnGenome.java:46).
 struct alignas(64) OccBlock {
   uint32_t cnt[4];
-  uint64_t lo[2];
-  uint64_t hi[2];
+  uint64_t h0[2];     // {lo, hi} of positions [0, 64)
+  uint64_t h1[2];     // {lo, hi} of positions [64, 128)
   uint64_t nmask[2];
 };
 static_assert(sizeof(OccBlock) == 64, "OccBlock must be one 64-byte burst");
+enum : int32_t { kOccFlagged = 0, kOccPlain = 1 };  // IndexView::occMode
+// How a caller may read a flagged index instead (loadBlock's mode, never an IndexView::occMode): the
+// N word always, with the other two loads and without the branch on the has-N bit (occEager)
+enum : int32_t { kOccEager = 2 };
+GWA_HD int occEager(int occMode) { return occMode == kOccFlagged ? kOccEager : occMode; }
+constexpr uint32_t kOccHasN = 0x80000000u;          // kOccFlagged: in cnt[0]
+// true when the has-N bit is free: the totals of A,C,G,T (C = CharacterCount.C), the up to 64
+// positions past the text's end that the last block counts as A included
+GWA_HD bool occCountsFit(const uint64_t C[5]) {
+  for (int c = 0; c < 4; ++c)
+    if (C[c + 1] - C[c] + 64 >= (uint64_t)kOccHasN) return false;
+  return true;
+}
 
 struct IndexView {
   const OccBlock *occ[2];  // [0] forward index (BWT of T), [1] reverse index (BWT of reverse(T))
@@ -44,6 +66,7 @@ struct IndexView {
   const int64_t *contigOff;
   int32_t nContig;
   int32_t kmerK;           // k of the k-mer interval tables (0 = none)
+  int32_t occMode;         // kOccFlagged (0) / kOccPlain: how the Occ blocks were built (OccBlock)
   uint64_t N;
   uint64_t C[5];  // CharacterCount.C (A/CharacterCount.java:41-50); identical for both strands
   // Per index: the suffix interval reached by kmerK backward-search steps from [0, N) over each

@@ -128,7 +128,7 @@ bool cyclicSAHost(const uint8_t *codes, uint64_t n, std::vector<uint32_t> &sa, i
   return true;
 }
 
-static void buildOcc(const std::vector<uint8_t> &T, const std::vector<uint32_t> &SA, std::vector<OccBlock> &occ) {
+static void buildOcc(const std::vector<uint8_t> &T, const std::vector<uint32_t> &SA, int occMode, std::vector<OccBlock> &occ) {
   const uint64_t n = T.size();
   const uint64_t nb = n / 128 + 1;
   occ.assign(nb, OccBlock());
@@ -136,20 +136,29 @@ static void buildOcc(const std::vector<uint8_t> &T, const std::vector<uint32_t> 
   uint32_t cnt[4] = {0, 0, 0, 0};
   for (uint64_t b = 0; b < nb; ++b) {
     OccBlock &B = occ[b];
-    for (int c = 0; c < 4; ++c) B.cnt[c] = cnt[c];
+    const uint64_t mid = b * 128 + 64;
     for (uint64_t p = b * 128; p < std::min<uint64_t>(n, (b + 1) * 128); ++p) {
+      if (p == mid)
+        for (int c = 0; c < 4; ++c) B.cnt[c] = cnt[c];
       // BWT[p] = T[(SA[p] - 1 + n) % n]   (A/BWTransform.java:172-179)
       uint64_t src = SA[p] == 0 ? n - 1 : SA[p] - 1;
       uint8_t c = T[src];
       int r = (int)(p - b * 128);
+      uint64_t *h = r < 64 ? B.h0 : B.h1;
       if (c >= 4) {
         B.nmask[r >> 6] |= 1ULL << (r & 63);
       } else {
-        if (c & 1) B.lo[r >> 6] |= 1ULL << (r & 63);
-        if (c & 2) B.hi[r >> 6] |= 1ULL << (r & 63);
+        if (c & 1) h[0] |= 1ULL << (r & 63);
+        if (c & 2) h[1] |= 1ULL << (r & 63);
         cnt[c]++;
       }
     }
+    if (n <= mid) {
+      // the text ends in the first half: the positions [n, mid) read as A in the planes
+      for (int c = 0; c < 4; ++c) B.cnt[c] = cnt[c];
+      B.cnt[0] += (uint32_t)(mid - n);
+    }
+    if (occMode == kOccFlagged && (B.nmask[0] | B.nmask[1])) B.cnt[0] |= kOccHasN;
   }
 }
 
@@ -157,12 +166,13 @@ void finishIndex(HostIndex &ix) {
   const uint64_t n = ix.N;
   std::vector<uint8_t> R(n);
   for (uint64_t i = 0; i < n; ++i) R[i] = ix.T[n - 1 - i];
-  buildOcc(ix.T, ix.sa[0], ix.occ[0]);
-  buildOcc(R, ix.sa[1], ix.occ[1]);
   uint64_t count[5] = {0, 0, 0, 0, 0};
   for (uint64_t i = 0; i < n; ++i) count[ix.T[i] > 4 ? 4 : ix.T[i]]++;
   uint64_t sum = 0;
   for (int c = 0; c < 5; ++c) { ix.C[c] = sum; sum += count[c]; }
+  if (!occCountsFit(ix.C)) ix.occMode = kOccPlain;
+  buildOcc(ix.T, ix.sa[0], ix.occMode, ix.occ[0]);
+  buildOcc(R, ix.sa[1], ix.occMode, ix.occ[1]);
   ix.text2.assign(n / 32 + 2, 0);
   ix.textN.assign(n / 64 + 2, 0);
   for (uint64_t i = 0; i < n; ++i) {

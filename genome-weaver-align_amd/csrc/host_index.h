@@ -17,6 +17,9 @@ struct HostIndex {
   std::vector<int32_t> chrRank;  // String.compareTo rank of each contig name
   std::vector<uint32_t> sa[2];   // cyclic SA of T and of reverse(T)
   std::vector<OccBlock> occ[2];
+  // IndexView::occMode of occ[].  finishIndex keeps kOccPlain when the caller set it (tests force
+  // the mode this way) and falls back to it when the symbol counts leave no room for the has-N bit
+  int32_t occMode = kOccFlagged;
   std::vector<uint64_t> text2, textN;
   uint64_t C[5] = {0, 0, 0, 0, 0};
 };

@@ -90,16 +90,20 @@ struct Cnt4Plus {
   }
 };
 
-// One lane per 128 BWT positions: BWT[p] = T[(SA[p]-1) mod N] (A/BWTransform.java:172-179)
-__global__ void occLocal(const uint8_t *__restrict__ T, const uint32_t *__restrict__ SA, uint64_t N, uint64_t nb,
+// One lane per 128 BWT positions: BWT[p] = T[(SA[p]-1) mod N] (A/BWTransform.java:172-179).
+// The block's cnt[] leave here as the counts of its FIRST HALF alone -- the positions past the
+// text's end counted as A, as the planes show them -- with the has-N bit (flagged mode) already in
+// cnt[0]; occCounts adds the counts of the blocks before (OccBlock, gwa_layout.h).
+__global__ void occLocal(const uint8_t *__restrict__ T, const uint32_t *__restrict__ SA, uint64_t N, uint64_t nb, int occMode,
                          OccBlock *__restrict__ occ, Cnt4 *__restrict__ local) {
   for (uint64_t b = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; b < nb; b += (uint64_t)gridDim.x * blockDim.x) {
     uint64_t lo[2] = {0, 0}, hi[2] = {0, 0}, nm[2] = {0, 0};
-    Cnt4 c = {{0, 0, 0, 0}};
+    Cnt4 c = {{0, 0, 0, 0}}, h0 = {{0, 0, 0, 0}};
     const uint64_t p0 = b * 128;
     for (int r = 0; r < 128; ++r) {
       uint64_t p = p0 + r;
       if (p >= N) break;
+      if (r == 64) h0 = c;
       uint64_t s = SA[p];
       uint8_t ch = T[s == 0 ? N - 1 : s - 1];
       if (ch >= 4) {
@@ -110,15 +114,22 @@ __global__ void occLocal(const uint8_t *__restrict__ T, const uint32_t *__restri
         c.c[ch]++;
       }
     }
+    if (N <= p0 + 64) {  // the text ends in the first half (p0 <= N: the last block)
+      h0 = c;
+      h0.c[0] += (uint32_t)(p0 + 64 - N);
+    }
+    if (occMode == kOccFlagged && (nm[0] | nm[1])) h0.c[0] |= kOccHasN;
     OccBlock &B = occ[b];
-    B.lo[0] = lo[0]; B.lo[1] = lo[1]; B.hi[0] = hi[0]; B.hi[1] = hi[1]; B.nmask[0] = nm[0]; B.nmask[1] = nm[1];
+    B.h0[0] = lo[0]; B.h0[1] = hi[0]; B.h1[0] = lo[1]; B.h1[1] = hi[1]; B.nmask[0] = nm[0]; B.nmask[1] = nm[1];
+    for (int i = 0; i < 4; ++i) B.cnt[i] = h0.c[i];
     local[b] = c;
   }
 }
 
+// (the sum cannot carry into the has-N bit: the build chose the flagged mode by occCountsFit)
 __global__ void occCounts(const Cnt4 *__restrict__ excl, uint64_t nb, OccBlock *__restrict__ occ) {
   for (uint64_t b = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; b < nb; b += (uint64_t)gridDim.x * blockDim.x)
-    for (int i = 0; i < 4; ++i) occ[b].cnt[i] = excl[b].c[i];
+    for (int i = 0; i < 4; ++i) occ[b].cnt[i] += excl[b].c[i];
 }
 
 // 2-bit text (32 codes per word, LSB-first) + N bitmap (64 per word)
@@ -233,13 +244,13 @@ void reverseTextGpu(const uint8_t *d_T, uint64_t N, uint8_t *d_R, hipStream_t s)
   SCHK(hipGetLastError());
 }
 
-// Occ blocks of the BWT of d_T under d_sa; fills d_occ[0 .. N/128]
-void buildOccGpu(const uint8_t *d_T, const uint32_t *d_sa, uint64_t N, OccBlock *d_occ, hipStream_t s) {
+// Occ blocks of the BWT of d_T under d_sa, in mode occMode (IndexView::occMode); fills d_occ[0 .. N/128]
+void buildOccGpu(const uint8_t *d_T, const uint32_t *d_sa, uint64_t N, int occMode, OccBlock *d_occ, hipStream_t s) {
   const uint64_t nb = N / 128 + 1;
   Cnt4 *local = nullptr;
   SCHK(hipMalloc(&local, nb * sizeof(Cnt4)));
   const unsigned g = gridFor(nb);
-  hipLaunchKernelGGL(occLocal, dim3(g > 65536 ? 65536 : g), dim3(256), 0, s, d_T, d_sa, N, nb, d_occ, local);
+  hipLaunchKernelGGL(occLocal, dim3(g > 65536 ? 65536 : g), dim3(256), 0, s, d_T, d_sa, N, nb, occMode, d_occ, local);
   SCHK(hipGetLastError());
   size_t bytes = 0;
   Cnt4 zero = {{0, 0, 0, 0}};

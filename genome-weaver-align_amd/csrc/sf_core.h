@@ -227,9 +227,13 @@ struct SfLane : BsfLane<R, QW, DPM == 2, 24, DPM> {
         tp = tp == 0 ? ix.N - 1 : tp - 1;
       } else {
         // backwardSearch(ch, si) = C[ch] + getOcc(ch, lb|ub) (A/FMIndexOnOccTable.java:47-51)
+        // (N words read eagerly, as in BsfLane::rank2: no divergent branch in this loop)
+        const int md = occEager(ix.occMode);
         Block B0, B1;
-        loadBlock(ix.occ[fm], lb >> 7, B0);
-        loadBlock(ix.occ[fm], ub >> 7, B1);
+        loadBlock(ix.occ[fm], lb, md, B0);
+        loadBlock(ix.occ[fm], ub, md, B1);
+        finishBlock(ix.occ[fm], lb, md, B0);
+        finishBlock(ix.occ[fm], ub, md, B1);
         blocks += 1 + ((lb >> 7) != (ub >> 7) ? 1 : 0);
         const uint64_t nlb = ix.C[ch] + rankOne(B0, lb, ch), nub = ix.C[ch] + rankOne(B1, ub, ch);
         miss = nlb >= nub ? 1 : 0;

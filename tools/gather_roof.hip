@@ -53,6 +53,49 @@ __global__ void __launch_bounds__(256) g_block64(const u32x4 *buf, uint64_t nblo
   if (acc == 0x12345678u) out[0] = (uint32_t)g;
 }
 
+// Fewer than four 16-B pieces of each random 64-B block: what a rank costs when the block layout
+// lets a lane fetch only the pieces it needs.  The block (one 64-B fabric request) is the same as
+// in g_block64; only the number of load instructions per block and which pieces they name differ:
+//   P1      piece 0
+//   P2SEL   piece 0 + piece 1 or 2, chosen per lane per access (counts first, then one of two halves)
+//   P2ADJ   pieces s, s + 1 with s = 0 or 1 per lane per access (counts between the two halves)
+//   P3      piece 0 + piece 1 or 2 + piece 3 (the P2SEL shape with the N-bitmap quarter always read)
+enum { P1 = 0, P2SEL = 1, P2ADJ = 2, P3 = 3 };
+template <int D, int SHAPE>
+__global__ void __launch_bounds__(256) g_pieces(const u32x4 *buf, uint64_t nblocks, int rounds, uint32_t *out) {
+  constexpr int NP = SHAPE == P1 ? 1 : SHAPE == P3 ? 3 : 2;
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint64_t st[D];
+#pragma unroll
+  for (int d = 0; d < D; ++d) st[d] = mix(g * D + d + 0x1357);
+  uint32_t acc = 0;
+  for (int r = 0; r < rounds; ++r) {
+    u32x4 v[D][NP];
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      const u32x4 *p = buf + ((st[d] >> 20) & (nblocks - 1)) * 4;
+      const uint32_t s = (uint32_t)(st[d] >> 19) & 1u;  // the half this access needs
+      if constexpr (SHAPE == P2ADJ) {
+        v[d][0] = __builtin_nontemporal_load(p + s);
+        v[d][1] = __builtin_nontemporal_load(p + s + 1);
+      } else {
+        v[d][0] = __builtin_nontemporal_load(p);
+        if constexpr (NP >= 2) v[d][1] = __builtin_nontemporal_load(p + 1 + s);
+        if constexpr (NP >= 3) v[d][2] = __builtin_nontemporal_load(p + 3);
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      uint32_t x = v[d][0].x;
+      if constexpr (NP >= 2) x ^= v[d][1].y;
+      if constexpr (NP >= 3) x ^= v[d][2].w;
+      acc += x;
+      st[d] = st[d] * 6364136223846793005ULL + (1442695040888963407ULL ^ x);
+    }
+  }
+  if (acc == 0x12345678u) out[0] = (uint32_t)g;
+}
+
 // The same random 64-B blocks, loaded cooperatively by the 4 lanes of a quad: for each of the
 // quad's 4 blocks in turn, lane q of the quad loads bytes [16q, 16q + 16) of it, so one load
 // instruction covers 16 whole blocks (one 64-B line each) instead of 64 quarter blocks.  The owner
@@ -167,6 +210,14 @@ int main() {
   RUN("block64", 1, hipLaunchKernelGGL(g_block64<1>, grid, blk, 0, 0, (const u32x4 *)buf, bytes / 64, rounds, out), 64.0)
   RUN("block64", 2, hipLaunchKernelGGL(g_block64<2>, grid, blk, 0, 0, (const u32x4 *)buf, bytes / 64, rounds, out), 64.0)
   RUN("block64", 4, hipLaunchKernelGGL(g_block64<4>, grid, blk, 0, 0, (const u32x4 *)buf, bytes / 64, rounds, out), 64.0)
+#define RUNP(KIND, SHAPE)                                                                            \
+  RUN(KIND, 1, hipLaunchKernelGGL((g_pieces<1, SHAPE>), grid, blk, 0, 0, (const u32x4 *)buf, bytes / 64, rounds, out), 64.0) \
+  RUN(KIND, 2, hipLaunchKernelGGL((g_pieces<2, SHAPE>), grid, blk, 0, 0, (const u32x4 *)buf, bytes / 64, rounds, out), 64.0) \
+  RUN(KIND, 4, hipLaunchKernelGGL((g_pieces<4, SHAPE>), grid, blk, 0, 0, (const u32x4 *)buf, bytes / 64, rounds, out), 64.0)
+  RUNP("piece1", P1)
+  RUNP("piece2sel", P2SEL)
+  RUNP("piece2adj", P2ADJ)
+  RUNP("piece3", P3)
   RUN("block64quad", 1, hipLaunchKernelGGL(g_block64_quad<1>, grid, blk, 0, 0, (const u32x4 *)buf, bytes / 64, rounds, out), 64.0)
   RUN("block64quad", 2, hipLaunchKernelGGL(g_block64_quad<2>, grid, blk, 0, 0, (const u32x4 *)buf, bytes / 64, rounds, out), 64.0)
   RUN("word8", 1, hipLaunchKernelGGL(g_word8<1>, grid, blk, 0, 0, (const uint64_t *)buf, bytes / 8, rounds, out), 64.0)
