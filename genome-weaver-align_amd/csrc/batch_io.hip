@@ -199,12 +199,19 @@ __device__ __forceinline__ uint64_t lineAt(const char *__restrict__ t, uint64_t 
   return i + 1;
 }
 
-__global__ void __launch_bounds__(256) fastqFieldsKernel(const char *__restrict__ t, uint64_t len, const uint64_t *__restrict__ start,
-                                                         uint32_t n, uint64_t *__restrict__ f, uint32_t *__restrict__ err) {
+// Two segments (a paired batch: mate 1's slice, then mate 2's at base2): records [0, n1) lie in
+// [0, end1), records [n1, n) in [base2, len) with their starts relative to base2.  Every line is
+// bounded by the end of its record's own segment -- a first segment whose last line has no newline
+// must not run on into the bytes behind it.  One segment: n1 = n, end1 = len, base2 = 0.
+__global__ void __launch_bounds__(256) fastqFieldsKernel(const char *__restrict__ t, uint64_t total, const uint64_t *__restrict__ start,
+                                                         uint32_t n, uint64_t *__restrict__ f, uint32_t *__restrict__ err,
+                                                         uint32_t n1, uint64_t end1, uint64_t base2) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n) return;
   uint64_t he, se, pe, qe;
-  const uint64_t hb = start[r];
+  const bool second = r >= n1;
+  const uint64_t len = second ? total : end1;
+  const uint64_t hb = start[r] + (second ? base2 : 0);
   const uint64_t sb = lineAt(t, len, hb, &he);
   const uint64_t pb = lineAt(t, len, sb, &se);
   const uint64_t qb = lineAt(t, len, pb, &pe);
@@ -226,7 +233,44 @@ __global__ void __launch_bounds__(256) fastqFieldsKernel(const char *__restrict_
 void launchFastqFields(const char *text, uint64_t len, const uint64_t *start, uint32_t n, uint64_t *fields,
                        uint32_t *err, hipStream_t s) {
   if (n == 0) return;
-  hipLaunchKernelGGL(fastqFieldsKernel, dim3((n + 255) / 256), dim3(256), 0, s, text, len, start, n, fields, err);
+  hipLaunchKernelGGL(fastqFieldsKernel, dim3((n + 255) / 256), dim3(256), 0, s, text, len, start, n, fields, err, n,
+                     len, (uint64_t)0);
+  FCHK(hipGetLastError());
+}
+
+void launchFastqFieldsPair(const char *text, uint64_t len1, uint64_t base2, uint64_t len2, const uint64_t *start,
+                           uint32_t np, uint64_t *fields, uint32_t *err, hipStream_t s) {
+  if (np == 0) return;
+  const uint32_t n = 2 * np;
+  hipLaunchKernelGGL(fastqFieldsKernel, dim3((n + 255) / 256), dim3(256), 0, s, text, base2 + len2, start, n, fields, err,
+                     np, len1, base2);
+  FCHK(hipGetLastError());
+}
+
+// Mate names of a paired batch (mate 1 of pair i = read i, mate 2 = read np + i; text or blob
+// batches alike): one pair per lane, each name without one trailing "/1" or "/2"; the lowest pair
+// whose names differ goes to err.
+__device__ __forceinline__ uint64_t mateNameEnd(const char *__restrict__ t, uint64_t b, uint64_t e) {
+  if (e - b >= 2 && t[e - 2] == '/' && (t[e - 1] == '1' || t[e - 1] == '2')) return e - 2;
+  return e;
+}
+
+__global__ void __launch_bounds__(256) mateNameKernel(const char *__restrict__ t, const uint64_t *__restrict__ nameB,
+                                                      const uint64_t *__restrict__ nameE, uint32_t np,
+                                                      uint32_t *__restrict__ err) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= np) return;
+  const uint64_t b1 = nameB[i], b2 = nameB[(size_t)np + i];
+  const uint64_t e1 = mateNameEnd(t, b1, nameE[i]), e2 = mateNameEnd(t, b2, nameE[(size_t)np + i]);
+  bool same = e1 - b1 == e2 - b2;
+  for (uint64_t k = 0; same && k < e1 - b1; ++k) same = t[b1 + k] == t[b2 + k];
+  if (!same) atomicMin(err, i);
+}
+
+void launchMateNames(const char *nameText, const uint64_t *nameB, const uint64_t *nameE, uint32_t np, uint32_t *err,
+                     hipStream_t s) {
+  if (np == 0) return;
+  hipLaunchKernelGGL(mateNameKernel, dim3((np + 255) / 256), dim3(256), 0, s, nameText, nameB, nameE, np, err);
   FCHK(hipGetLastError());
 }
 

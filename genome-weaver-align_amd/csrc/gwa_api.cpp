@@ -955,6 +955,126 @@ int batchCreateFastq(gwa_index_t *ix, const gwa_config_t *cfg, const char *text,
     return fail(e.what());
   }
 }
+
+// Pipeline use: a paired-end batch (gwa_batch_create_pairs) from the FASTQ text of np complete
+// mate-1 records and np complete mate-2 records, without a host parse or a host copy: both slices
+// go from the caller's (pinned) buffers into one device allocation, the second behind the first at a
+// 16-B boundary (and behind the 32 bytes of room the 16-B chunk loads take after a text), and the
+// fields of all 2 np records are located there in one launch -- record i is mate 1 of pair i,
+// record np + i its mate 2, the layout the pairing kernels and samPair read.  start1[i] / start2[i]:
+// the header lines, relative to their own text.  text2 == nullptr: one text holding both mates
+// (an interleaved file), start1 = the np mate-1 starts, then the np mate-2 starts.  A malformed
+// record fails with the host parser's message after the label (file name) of its text.
+int batchCreatePairsFastq(gwa_index_t *ix, const gwa_config_t *cfg, const char *text1, uint64_t len1,
+                          const uint64_t *start1, const char *text2, uint64_t len2, const uint64_t *start2, uint32_t np,
+                          int32_t minInsert, int32_t maxInsert, const char *label1, const char *label2,
+                          gwa_batch_t **out) {
+  auto *b = new gwa_batch();
+  try {
+    if (cfg->strategy != 0) throw std::runtime_error("paired-end alignment runs the -m bsf search");
+    if (minInsert < 0 || maxInsert < minInsert) throw std::runtime_error("bad insert-size range");
+    if (np > 0x7FFFFFFFu) throw std::runtime_error("paired-end batch too large");
+    gwa_config_t c = *cfg;
+    c.report_type = 1;  // every best hit of a mate is a pairing candidate
+    const uint32_t n = 2 * np;
+    (void)batchHead(ix, &c, n, b);  // (-m bsf: never header-only)
+    b->hasQual = true;
+    hipStream_t s = b->stream;
+    const bool two = text2 != nullptr;
+    const uint64_t base2 = two ? (len1 + 32 + 15) & ~(uint64_t)15 : 0;
+    const uint64_t total = two ? base2 + len2 : len1;
+    char *dText = bAlloc<char>(total + 32);  // (+32: the device reads the text in aligned 16-B chunks)
+    b->d_seqText = dText;
+    if (len1) HIPCHK(hipMemcpyAsync(dText, text1, len1, hipMemcpyHostToDevice, s));
+    if (two && len2) HIPCHK(hipMemcpyAsync(dText + base2, text2, len2, hipMemcpyHostToDevice, s));
+    uint64_t *dStart = bAlloc<uint64_t>(n ? n : 1);
+    if (two) {
+      if (np) HIPCHK(hipMemcpyAsync(dStart, start1, (size_t)np * 8, hipMemcpyHostToDevice, s));
+      if (np) HIPCHK(hipMemcpyAsync(dStart + np, start2, (size_t)np * 8, hipMemcpyHostToDevice, s));
+    } else if (n) {
+      HIPCHK(hipMemcpyAsync(dStart, start1, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    }
+    uint64_t *f = bAlloc<uint64_t>(n ? 6 * (size_t)n : 1);
+    b->d_fieldOwn[0] = f;
+    uint32_t *dErr = bAlloc<uint32_t>(1);
+    uint32_t err = 0;
+    HIPCHK(hipMemsetAsync(dErr, 0xFF, 4, s));
+    launchFastqFieldsPair(dText, len1, base2, two ? len2 : len1, dStart, np, f, dErr, s);
+    HIPCHK(hipMemcpyAsync(&err, dErr, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    batchFree(dStart, nullptr);  // (the stream was synchronised above)
+    batchFree(dErr, nullptr);
+    if (err != 0xFFFFFFFFu) {  // the host parser words the error
+      const bool inSecond = two && err >= np;
+      const std::string label = (inSecond ? label2 : label1) ? std::string(inSecond ? label2 : label1) + ": " : std::string();
+      gwa_read_buf_t pb{};
+      uint64_t used = 0;
+      if (gwa_reads_parse(inSecond ? text2 : text1, inSecond ? len2 : len1, 1, 1, &pb, &used) != 0)
+        throw std::runtime_error(label + gwa_last_error());
+      gwa_reads_free(&pb);
+      throw std::runtime_error(label + "malformed FASTQ record " + std::to_string(inSecond ? err - np : err));
+    }
+    b->d_nameText = dText;
+    b->d_qualText = dText;
+    b->d_nameB = f;
+    b->d_nameE = f + n;
+    b->d_seqB = f + 2 * (size_t)n;
+    b->d_seqE = f + 3 * (size_t)n;
+    b->d_qualB = f + 4 * (size_t)n;
+    b->d_qualE = f + 5 * (size_t)n;
+    batchTail(b, total);  // (an upper bound of the bases: the codes buffer is sized from it)
+    b->pairs = np;
+    b->minIns = minInsert;
+    b->maxIns = maxInsert;
+    b->d_rescue = bAlloc<RescueOut>(np ? np : 1);
+    b->d_heavy = bAlloc<uint32_t>((size_t)np + 2);  // list, its count, rescues skipped (window)
+    *out = b;
+    return 0;
+  } catch (std::exception &e) {
+    freeBatchDev(b);
+    delete b;
+    return fail(e.what());
+  }
+}
+
+// The mate-name check of a paired batch (GWA_PAIR_CHECK_NAMES): true when some pair's mate names
+// differ after one trailing "/1" or "/2" is taken off each; *pair = the lowest such pair of the
+// batch, with both names as they stand in the input.
+bool batchMateNamesDiffer(gwa_batch_t *b, uint32_t *pair, std::string *name1, std::string *name2) {
+  const uint32_t np = b->pairs;
+  if (!np || !b->d_nameText) return false;
+  HIPCHK(hipSetDevice(b->ix->device));
+  hipStream_t s = b->stream;
+  uint32_t *dErr = bAlloc<uint32_t>(1);
+  uint32_t err = 0;
+  try {
+    HIPCHK(hipMemsetAsync(dErr, 0xFF, 4, s));
+    launchMateNames(b->d_nameText, b->d_nameB, b->d_nameE, np, dErr, s);
+    HIPCHK(hipMemcpyAsync(&err, dErr, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+  } catch (...) {
+    (void)hipStreamSynchronize(s);
+    batchFree(dErr, nullptr);
+    throw;
+  }
+  batchFree(dErr, nullptr);
+  if (err == 0xFFFFFFFFu) return false;
+  *pair = err;
+  std::string *names[2] = {name1, name2};
+  for (int k = 0; k < 2; ++k) {
+    const size_t r = (size_t)k * np + err;
+    uint64_t be[2];
+    HIPCHK(hipMemcpyAsync(&be[0], b->d_nameB + r, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&be[1], b->d_nameE + r, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    names[k]->assign((size_t)(be[1] - be[0]), '\0');
+    if (be[1] > be[0]) {
+      HIPCHK(hipMemcpyAsync(&(*names[k])[0], b->d_nameText + be[0], be[1] - be[0], hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+    }
+  }
+  return true;
+}
 }  // namespace gwa
 
 extern "C" {

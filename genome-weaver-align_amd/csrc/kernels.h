@@ -38,6 +38,13 @@ void launchEncode(const char *seq, const uint64_t *seqB, const uint64_t *seqE, u
                   size_t scanTmpBytes, int pass, hipStream_t s);
 void launchFastqFields(const char *text, uint64_t len, const uint64_t *start, uint32_t n, uint64_t *fields,
                        uint32_t *err, hipStream_t s);
+// the same over a paired batch's two text segments: np mate-1 records in [0, len1), np mate-2 records
+// in [base2, base2 + len2), their starts (start[np + i]) relative to base2
+void launchFastqFieldsPair(const char *text, uint64_t len1, uint64_t base2, uint64_t len2, const uint64_t *start,
+                           uint32_t np, uint64_t *fields, uint32_t *err, hipStream_t s);
+// mate names of np pairs compared (a trailing "/1" or "/2" apart): *err = min(*err, lowest differing pair)
+void launchMateNames(const char *nameText, const uint64_t *nameB, const uint64_t *nameE, uint32_t np, uint32_t *err,
+                     hipStream_t s);
 size_t encodeScanTempBytes(uint32_t n);
 struct PairSpec {  // paired-end formatting: np pairs (mate 1 = read i, mate 2 = read np + i); np = 0: single-end
   uint32_t np;

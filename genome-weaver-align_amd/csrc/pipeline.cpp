@@ -13,10 +13,14 @@
 // batches' kernels concurrently, each batch on its own stream and search scratch (gwa_api.cpp
 // Scratch), so one batch's set-up, deep-tier tail and SAM formatting overlap another's kernels.  At
 // most `depth` batches are in flight, which bounds memory.
+//
+// Paired-end input takes the same route with pair batches: two mate files (or one interleaved file)
+// are read and framed by record_stream.cpp, which zips slice k of the one with slice k of the other;
+// a worker puts both slices' FASTQ text into one device allocation (gwa_api.cpp
+// batchCreatePairsFastq) and the batch's SAM holds two lines per pair.
 #include <hip/hip_runtime.h>
-#include <zlib.h>
 
-#include "snappy_stream.h"
+#include "record_stream.h"
 
 #include <algorithm>
 #include <atomic>
@@ -43,15 +47,16 @@
 extern "C" int gwa_fail_message(const char *msg);  // gwa_api.cpp
 
 namespace gwa {
-uint64_t frameRecords(const char *t, uint64_t len, int format, bool final, uint64_t maxRec, uint64_t *nRec,
-                      std::vector<uint64_t> *starts);
-void newlinePositions(const char *t, uint64_t a, uint64_t b, std::vector<uint64_t> &out);
-void newlineCount(const char *t, uint64_t a, uint64_t b, uint64_t *count, bool *blank, bool *cr);
-void recordStartsFromNewlines(const char *t, uint64_t a, uint64_t b, uint64_t g0, uint64_t *starts, uint64_t cap);
-uint64_t frameFastqLines(const char *t, uint64_t len, const std::vector<uint64_t> &nl, bool final, uint64_t maxRec,
-                         uint64_t *nRec, std::vector<uint64_t> *starts);
 int batchCreateFastq(gwa_index_t *ix, const gwa_config_t *cfg, const char *text, uint64_t len, const uint64_t *start,
                      uint32_t n, gwa_batch_t **out);
+// a paired batch from the mates' FASTQ text: two segments, or (text2 == nullptr) one interleaved
+// segment whose start1 holds the np mate-1 starts and then the np mate-2 starts (gwa_api.cpp)
+int batchCreatePairsFastq(gwa_index_t *ix, const gwa_config_t *cfg, const char *text1, uint64_t len1,
+                          const uint64_t *start1, const char *text2, uint64_t len2, const uint64_t *start2, uint32_t np,
+                          int32_t minInsert, int32_t maxInsert, const char *label1, const char *label2,
+                          gwa_batch_t **out);
+// the lowest pair of a paired batch whose mate names differ (false: none)
+bool batchMateNamesDiffer(gwa_batch_t *b, uint32_t *pair, std::string *name1, std::string *name2);
 uint64_t batchSamInto(gwa_batch_t *b, char **buf, uint64_t *cap);  // gwa_api.cpp
 void pinnedFree(char *p);
 char *pinnedAlloc(uint64_t bytes);
@@ -62,18 +67,16 @@ namespace {
 using Clock = std::chrono::steady_clock;
 double secs(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
 
-// A buffer of read-file text.  Pinned host memory makes the batch's H2D copy one DMA instead of a
+// Read-file text lives in pooled buffers (record_stream.h TextBuf).  Pinned host memory makes the
+// batch's H2D copy one DMA instead of a
 // staged pageable copy, which the runtime serialises across worker threads (measured: set-up 0.36 s
 // -> 0.21 s and 11 -> 22 M reads/s FASTQ -> SAM for 10M reads).  Pinning takes about a second per
 // 5 GB; gwa_pipeline_open pins the buffers a run keeps in flight, and the pool falls back to pageable
 // buffers beyond them.  Buffers are recycled when the last job that references one is done, and kept
 // across align_file calls.
-struct TextBuf {
-  char *p = nullptr;
-  size_t cap = 0, size = 0;
-  bool pinned = false;
-  const char *data() const { return p; }
-};
+using gwa::TextBuf;
+using gwa::compressedKind;
+using gwa::formatOf;
 
 class BufPool {
   std::mutex mu;
@@ -181,6 +184,52 @@ struct Job {
   uint64_t tb = 0, te = 0;
   int format = 1;
   std::vector<uint64_t> starts;  // FASTQ: each record's header line, relative to tb
+  // paired-end (pairs > 0): mate 1 above, mate 2 here -- in-memory reads, or a second slice of file
+  // text; an interleaved slice has no second text and holds the mates alternating (2 * pairs records)
+  uint64_t pairs = 0;
+  gwa_reads_t reads2{};
+  std::shared_ptr<TextBuf> text2;
+  uint64_t tb2 = 0, te2 = 0;
+  int format2 = 1;
+  std::vector<uint64_t> starts2;
+};
+
+// a run's paired-end parameters (gwa_pipeline_align_pair_files / gwa_pipeline_align_pairs)
+struct PairSetup {
+  int32_t minInsert = 0, maxInsert = 0;
+  bool checkNames = false;
+  std::string label1, label2;  // the mate files, for error messages
+};
+
+// host copies of one mate set's reads (the mates of an interleaved FASTA slice, taken apart)
+struct HostReads {
+  std::string name, seq, qual;
+  std::vector<uint64_t> nameOff{0}, seqOff{0}, qualOff{0};
+  bool hasQual = false;
+  void add(const gwa_reads_t &r, uint32_t i) {
+    name.append(r.name + r.name_off[i], r.name_off[i + 1] - r.name_off[i]);
+    seq.append(r.seq + r.seq_off[i], r.seq_off[i + 1] - r.seq_off[i]);
+    nameOff.push_back(name.size());
+    seqOff.push_back(seq.size());
+    if (r.qual) {
+      hasQual = true;
+      qual.append(r.qual + r.qual_off[i], r.qual_off[i + 1] - r.qual_off[i]);
+      qualOff.push_back(qual.size());
+    }
+  }
+  gwa_reads_t view() const {
+    gwa_reads_t v{};
+    v.n = (uint32_t)(nameOff.size() - 1);
+    v.name = name.data();
+    v.seq = seq.data();
+    v.name_off = nameOff.data();
+    v.seq_off = seqOff.data();
+    if (hasQual) {
+      v.qual = qual.data();
+      v.qual_off = qualOff.data();
+    }
+    return v;
+  }
 };
 
 struct Result {
@@ -189,10 +238,6 @@ struct Result {
 };
 
 }  // namespace
-
-// read-file chunks (and the room before each for the records carried over from the previous one);
-// a smaller file reads in one chunk of its own size
-constexpr uint64_t kChunk = 256ull << 20, kReserve = 512ull << 20;
 
 namespace {
 // MemAvailable of /proc/meminfo in bytes (0 = unknown)
@@ -249,6 +294,12 @@ struct Run {
   uint64_t cursor = 0, nextOff = 0;         // first batch whose offset is not fixed yet, its offset
   uint64_t turn = 0;                        // non-seekable output: the batch that writes next
   std::atomic<uint64_t> fileReads{0}, fileBatches{0};
+  // paired-end runs.  A mate-name mismatch (GWA_PAIR_CHECK_NAMES) does not fail the run at once: the
+  // batches before it, which are all with their workers by then, finish first, so that the pair
+  // reported is the lowest of the whole input whatever order the batches complete in.
+  const PairSetup *pair = nullptr;
+  uint64_t nameFailId = ~0ull;  // lowest batch with a mismatch
+  std::string nameErr;
 
   explicit Run(gwa_pipeline *p_) : p(p_) {
     depth = std::max<size_t>(4, 2 * p->ix.size() * p->workersPerDevice);
@@ -264,8 +315,8 @@ struct Run {
   // producer side: blocks while `depth` batches are in flight; false once the run has failed
   bool push(Job &&j) {
     std::unique_lock<std::mutex> g(mu);
-    cv.wait(g, [&] { return failed || inflight < depth; });
-    if (failed) return false;
+    cv.wait(g, [&] { return failed || nameFailId != ~0ull || inflight < depth; });
+    if (failed || nameFailId != ~0ull) return false;
     ++inflight;
     jobs.push_back(std::move(j));
     cv.notify_all();
@@ -300,7 +351,8 @@ struct Run {
       if (rc == 0) {
         res.n = rd->n;
         gwa_batch_t *b = nullptr;
-        rc = gwa_batch_create(ix, &p->cfg, rd, &b);
+        rc = j.pairs ? gwa_batch_create_pairs(ix, &p->cfg, rd, &j.reads2, pair->minInsert, pair->maxInsert, &b)
+                     : gwa_batch_create(ix, &p->cfg, rd, &b);
         if (rc == 0) {
           const auto t0 = Clock::now();
           rc = gwa_batch_run(b);
@@ -342,13 +394,13 @@ struct Run {
           ++cursor;
         }
         cv.notify_all();
-        cv.wait(g, [&] { return failed || offs.count(id) != 0; });
-        if (failed) return;
+        cv.wait(g, [&] { return failed || nameFailId < id || offs.count(id) != 0; });
+        if (failed || nameFailId < id) return;
         off = offs[id];
         offs.erase(id);
       } else {
-        cv.wait(g, [&] { return failed || turn == id; });
-        if (failed) return;
+        cv.wait(g, [&] { return failed || nameFailId < id || turn == id; });
+        if (failed || nameFailId < id) return;
       }
     }
     const auto w1 = Clock::now();
@@ -389,13 +441,44 @@ struct Run {
           if (failed || jobs.empty()) break;
           j = std::move(jobs.front());
           jobs.pop_front();
+          if (j.id > nameFailId) {  // (a batch after a mate-name mismatch: not run)
+            --inflight;
+            cv.notify_all();
+            continue;
+          }
         }
         const auto t0 = Clock::now();
         gwa_batch_t *b = nullptr;
         int rc = 0;
         uint32_t nr = 0;
         auto t1 = t0;
-        if (j.format == 1) {  // FASTQ: the text itself goes to the device, fields located there
+        if (j.pairs) {
+          nr = (uint32_t)(2 * j.pairs);
+          rc = createPairBatch(ix, j, &b, &t1);
+          if (rc == 0 && pair->checkNames) {
+            uint32_t at = 0;
+            std::string n1, n2;
+            bool differ = false;
+            try {
+              differ = gwa::batchMateNamesDiffer(b, &at, &n1, &n2);
+            } catch (...) {
+              gwa_batch_free(b);
+              throw;
+            }
+            if (differ) {
+              gwa_batch_free(b);
+              std::lock_guard<std::mutex> g(mu);
+              if (j.id < nameFailId) {
+                nameFailId = j.id;
+                nameErr = "the mate names of pair " + std::to_string(j.id * p->batchReads + at) + " differ: '" + n1 +
+                          "' and '" + n2 + "'";
+              }
+              --inflight;
+              cv.notify_all();
+              continue;
+            }
+          }
+        } else if (j.format == 1) {  // FASTQ: the text itself goes to the device, fields located there
           nr = (uint32_t)j.starts.size();
           rc = gwa::batchCreateFastq(ix, &p->cfg, j.text->data() + j.tb, j.te - j.tb, j.starts.data(), nr, &b);
         } else {  // FASTA reads (multi-line records): parsed on the host
@@ -409,6 +492,7 @@ struct Run {
           gwa_reads_free(&parsed);
         }
         j.text.reset();
+        j.text2.reset();
         const auto t2 = Clock::now();
         if (rc == 0) rc = gwa_batch_run(b);
         const auto t3 = Clock::now();
@@ -445,6 +529,58 @@ struct Run {
     }
   }
 
+  // a paired batch from a job's two slices (or its one interleaved slice): FASTQ text goes to the
+  // device as it is; with a FASTA mate both slices are parsed on the host, as single-end FASTA is
+  int createPairBatch(gwa_index_t *ix, Job &j, gwa_batch_t **b, Clock::time_point *parsed) {
+    const uint32_t np = (uint32_t)j.pairs;
+    const char *t1 = j.text->data() + j.tb;
+    const bool inter = !j.text2;
+    if (j.format == 1 && (inter || j.format2 == 1)) {
+      if (inter) {  // mate-1 starts (even records), then mate-2 starts
+        std::vector<uint64_t> st(2 * (size_t)np);
+        for (uint32_t i = 0; i < np; ++i) {
+          st[i] = j.starts[2 * (size_t)i];
+          st[(size_t)np + i] = j.starts[2 * (size_t)i + 1];
+        }
+        return gwa::batchCreatePairsFastq(ix, &p->cfg, t1, j.te - j.tb, st.data(), nullptr, 0, nullptr, np,
+                                          pair->minInsert, pair->maxInsert, pair->label1.c_str(), nullptr, b);
+      }
+      return gwa::batchCreatePairsFastq(ix, &p->cfg, t1, j.te - j.tb, j.starts.data(), j.text2->data() + j.tb2,
+                                        j.te2 - j.tb2, j.starts2.data(), np, pair->minInsert, pair->maxInsert,
+                                        pair->label1.c_str(), pair->label2.c_str(), b);
+    }
+    gwa_read_buf_t p1{}, p2{};
+    uint64_t used = 0;
+    int rc = 0;
+    try {
+      if (gwa_reads_parse(t1, j.te - j.tb, j.format, 1, &p1, &used) != 0)
+        throw std::runtime_error(pair->label1 + ": " + gwa_last_error());
+      if (inter) {
+        if (p1.reads.n != 2 * np) throw std::runtime_error(pair->label1 + ": the records of a batch do not parse as framed");
+        HostReads m1, m2;
+        for (uint32_t i = 0; i < np; ++i) {
+          m1.add(p1.reads, 2 * i);
+          m2.add(p1.reads, 2 * i + 1);
+        }
+        *parsed = Clock::now();
+        const gwa_reads_t v1 = m1.view(), v2 = m2.view();
+        rc = gwa_batch_create_pairs(ix, &p->cfg, &v1, &v2, pair->minInsert, pair->maxInsert, b);
+      } else {
+        if (gwa_reads_parse(j.text2->data() + j.tb2, j.te2 - j.tb2, j.format2, 1, &p2, &used) != 0)
+          throw std::runtime_error(pair->label2 + ": " + gwa_last_error());
+        *parsed = Clock::now();
+        rc = gwa_batch_create_pairs(ix, &p->cfg, &p1.reads, &p2.reads, pair->minInsert, pair->maxInsert, b);
+      }
+    } catch (...) {
+      gwa_reads_free(&p1);
+      gwa_reads_free(&p2);
+      throw;
+    }
+    gwa_reads_free(&p1);
+    gwa_reads_free(&p2);
+    return rc;
+  }
+
   void startFile() {
     for (int w = 0; w < p->workersPerDevice; ++w)
       for (size_t d = 0; d < p->ix.size(); ++d) workers.emplace_back(&Run::fileWorker, this, (int)d);
@@ -476,27 +612,6 @@ struct Run {
     done.clear();
   }
 };
-
-// 1: gzip (.gz), 2: snappy-java (.snap, R/ReadReaderFactory.java:130-139), 0: plain
-int compressedKind(const char *path) {
-  const size_t n = strlen(path);
-  if (n > 3 && strcmp(path + n - 3, ".gz") == 0) return 1;
-  if (n > 5 && strcmp(path + n - 5, ".snap") == 0) return 2;
-  return 0;
-}
-
-int formatOf(const char *path) {
-  std::string s(path);
-  if (s.size() > 3 && s.compare(s.size() - 3, 3, ".gz") == 0) s.resize(s.size() - 3);
-  else if (s.size() > 5 && s.compare(s.size() - 5, 5, ".snap") == 0) s.resize(s.size() - 5);
-  auto ends = [&](const char *x) {
-    const size_t n = strlen(x);
-    return s.size() >= n && s.compare(s.size() - n, n, x) == 0;
-  };
-  if (ends(".fa") || ends(".fasta") || ends(".fan")) return 0;
-  if (ends(".fastq") || ends(".fq")) return 1;
-  throw std::runtime_error(std::string("Unsupported file type: ") + path);
-}
 
 // The first record start at or after byte x of a plain read file of `size` bytes (size when none):
 // FASTA, a line starting with '>'; FASTQ, a line starting with '@' whose next-but-one line starts
@@ -580,8 +695,32 @@ int gwa_pipeline_stats(const gwa_pipeline_t *p, gwa_pipeline_stats_t *st) {
   return 0;
 }
 
-int gwa_pipeline_align(gwa_pipeline_t *p, const gwa_reads_t *reads, gwa_results_t *out) {
+}  // extern "C"
+
+namespace {
+
+// reads [a, a + c) of a caller's gwa_reads_t
+gwa_reads_t sliceReads(const gwa_reads_t *reads, uint32_t a, uint32_t c) {
+  gwa_reads_t s = *reads;
+  s.n = c;
+  s.name_off = reads->name_off + a;
+  s.seq_off = reads->seq_off + a;
+  s.qual_off = reads->qual ? reads->qual_off + a : nullptr;
+  s.qual_null = reads->qual && reads->qual_null ? reads->qual_null + a : nullptr;
+  return s;
+}
+
+// what gwa_batch_create_pairs refuses, refused before a run starts
+void checkPairRun(const gwa_config_t &cfg, int32_t minInsert, int32_t maxInsert) {
+  if (cfg.strategy != 0) throw std::runtime_error("paired-end alignment runs the -m bsf search");
+  if (minInsert < 0 || maxInsert < minInsert) throw std::runtime_error("bad insert-size range");
+}
+
+// gwa_pipeline_align (mate2 == nullptr) and gwa_pipeline_align_pairs (units = pairs)
+int alignInMemory(gwa_pipeline_t *p, const gwa_reads_t *reads, const gwa_reads_t *mate2, const PairSetup *pair,
+                  gwa_results_t *out) {
   Run run(p);
+  run.pair = pair;
   std::thread feeder;
   try {
     const auto t0 = Clock::now();
@@ -593,12 +732,11 @@ int gwa_pipeline_align(gwa_pipeline_t *p, const gwa_reads_t *reads, gwa_results_
         Job j;
         j.id = i;
         const uint32_t a = (uint32_t)(i * p->batchReads), c = (uint32_t)std::min<uint64_t>(p->batchReads, n - a);
-        j.reads = *reads;
-        j.reads.n = c;
-        j.reads.name_off = reads->name_off + a;
-        j.reads.seq_off = reads->seq_off + a;
-        j.reads.qual_off = reads->qual ? reads->qual_off + a : nullptr;
-        j.reads.qual_null = reads->qual && reads->qual_null ? reads->qual_null + a : nullptr;
+        j.reads = sliceReads(reads, a, c);
+        if (mate2) {
+          j.pairs = c;
+          j.reads2 = sliceReads(mate2, a, c);
+        }
         if (!run.push(std::move(j))) break;
       }
       run.finishJobs();
@@ -621,7 +759,7 @@ int gwa_pipeline_align(gwa_pipeline_t *p, const gwa_reads_t *reads, gwa_results_
     out->n_reads = n;
     out->records = nullptr;
     out->n_records = 0;
-    out->paired = 0;
+    out->paired = mate2 ? 1 : 0;
     out->sam = (char *)malloc(total + 1);
     out->sam_len = total;
     out->line_off = (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)n + 1));
@@ -635,7 +773,7 @@ int gwa_pipeline_align(gwa_pipeline_t *p, const gwa_reads_t *reads, gwa_results_
     out->line_off[n] = pos;
     out->sam[total] = 0;
     p->stats = gwa_pipeline_stats_t{};
-    p->stats.reads = n;
+    p->stats.reads = mate2 ? 2 * (uint64_t)n : n;
     p->stats.batches = nb;
     p->stats.wall_s = secs(t0, Clock::now());
     p->stats.read_s = 0;
@@ -647,6 +785,28 @@ int gwa_pipeline_align(gwa_pipeline_t *p, const gwa_reads_t *reads, gwa_results_
     run.join();
     return gwa_fail_message(e.what());
   }
+}
+
+}  // namespace
+
+extern "C" {
+
+int gwa_pipeline_align(gwa_pipeline_t *p, const gwa_reads_t *reads, gwa_results_t *out) {
+  return alignInMemory(p, reads, nullptr, nullptr, out);
+}
+
+int gwa_pipeline_align_pairs(gwa_pipeline_t *p, const gwa_reads_t *mate1, const gwa_reads_t *mate2, int32_t min_insert,
+                             int32_t max_insert, gwa_results_t *out) {
+  try {
+    if (mate1->n != mate2->n) throw std::runtime_error("paired-end: the mate files hold different numbers of reads");
+    checkPairRun(p->cfg, min_insert, max_insert);
+  } catch (std::exception &e) {
+    return gwa_fail_message(e.what());
+  }
+  PairSetup ps;
+  ps.minInsert = min_insert;
+  ps.maxInsert = max_insert;
+  return alignInMemory(p, mate1, mate2, &ps, out);
 }
 
 int gwa_reads_shard_range(const char *path, uint32_t shard, uint32_t nshards, uint64_t *begin, uint64_t *end) {
@@ -681,331 +841,163 @@ int gwa_pipeline_align_file(gwa_pipeline_t *p, const char *path, int fd, uint64_
   return gwa_pipeline_align_file_range(p, path, fd, 0, ~0ull, n_reads);
 }
 
+}  // extern "C"
+
+namespace {
+
+// where a file run's SAM goes: batches are written at their offsets (pwrite) only to a regular file
+// opened without O_APPEND -- pwrite ignores the offset under O_APPEND (Linux) and would append in
+// completion order
+void setOutput(Run &run, int fd) {
+  struct stat sb;
+  const off_t pos0 = ::lseek(fd, 0, SEEK_CUR);
+  run.fd = fd;
+  const int fl = ::fcntl(fd, F_GETFL);
+  run.seekable = pos0 >= 0 && fl >= 0 && !(fl & O_APPEND) && ::fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
+  run.base = run.seekable ? (uint64_t)pos0 : 0;
+}
+
+// Pin the read-text buffers a run keeps in flight (read-ahead, the chunk being framed, the batches in
+// the workers) before it starts -- pinning while batches run stalls their copies in the runtime
+// (measured: FASTQ -> SAM 8 M reads/s with background pinning, 20-25 M with the buffers pinned
+// first) -- as many as the streams need, at most a quarter of the available host memory (one budget
+// for all the streams of a run), kept for later calls.  Beyond them runs use pageable buffers.
+// Buffers pinned by an earlier call for a smaller file cannot hold this run's chunks: they are
+// unpinned, and only the pinned buffers of at least bufCap bytes count.  Returns those.
+uint64_t pinReadBuffers(gwa_pipeline *p, const std::vector<gwa::RecordStream *> &streams) {
+  const uint64_t nbuf = 4 + (uint64_t)p->ix.size() * (uint64_t)p->workersPerDevice;
+  uint64_t need = 0, bufCap = 0;
+  for (const gwa::RecordStream *s : streams) {
+    need += s->fileBytes() ? std::min<uint64_t>(nbuf, s->fileBytes() / s->chunk() + 3) : nbuf;
+    bufCap = std::max(bufCap, s->bufBytes());
+  }
+  const uint64_t avail = memAvailable(), capB = avail ? avail / 4 : (8ull << 30);
+  uint64_t relN = 0, relB = 0;
+  p->pool.releasePinnedBelow(bufCap, &relN, &relB);
+  p->pinnedBufs -= std::min(p->pinnedBufs, relN);
+  p->pinnedBytes -= std::min(p->pinnedBytes, relB);
+  uint64_t usable = p->pool.countPinned(bufCap);
+  try {
+    while (usable < need && p->pinnedBytes + bufCap <= capB) {
+      p->pool.addPinned(bufCap);
+      ++p->pinnedBufs;
+      ++usable;
+      p->pinnedBytes += bufCap;
+    }
+  } catch (std::exception &) {  // (pinning failed: pageable buffers)
+  }
+  return usable;
+}
+
+// the end of a file run: workers joined, the output position, the counters
+void finishFileRun(gwa_pipeline *p, Run &run, int fd, Clock::time_point t0, double readS, double frameS,
+                   uint64_t pinnedUsable) {
+  run.finishJobs();
+  for (auto &t : run.workers) t.join();
+  run.workers.clear();
+  if (run.failed) throw std::runtime_error(run.err);
+  if (run.nameFailId != ~0ull) throw std::runtime_error(run.nameErr);
+  if (run.seekable) ::lseek(fd, (off_t)(run.base + run.nextOff), SEEK_SET);
+  gwa_pipeline_stats_t &st = p->stats;
+  st = gwa_pipeline_stats_t{};
+  st.reads = run.fileReads;
+  st.batches = run.fileBatches;
+  st.pinned_bufs = pinnedUsable;
+  st.wall_s = secs(t0, Clock::now());
+  st.read_s = readS;
+  st.frame_s = frameS;
+  for (size_t d = 0; d < p->ix.size() && d < 16; ++d) st.device_kernel_s[d] = run.devBusy[d];
+  st.parse_s = run.parseS;
+  st.setup_s = run.setupS;
+  st.format_s = run.formatS;
+  st.write_s = run.writeS;
+  st.order_wait_s = run.waitS;
+}
+
+}  // namespace
+
+extern "C" {
+
 int gwa_pipeline_align_file_range(gwa_pipeline_t *p, const char *path, int fd, uint64_t begin, uint64_t end,
                                   uint64_t *n_reads) {
-  BufPool &pool = p->pool;
   Run run(p);
-  gzFile f = nullptr;
-  std::unique_ptr<gwa::SnapReader> snap;
-  int in = -1;
   try {
-    const int fmt = formatOf(path);
-    const int ck = compressedKind(path);
-    const bool gz = ck != 0;  // (a compressed stream: gzip or snappy-java)
-    const bool whole = begin == 0 && end == ~0ull;
-    if (gz) {
-      if (!whole) throw std::runtime_error(std::string("a byte range needs an uncompressed read file: ") + path);
-      if (ck == 1) {
-        f = gzopen(path, "rb");
-        if (!f) throw std::runtime_error(std::string("cannot open ") + path);
-        gzbuffer(f, 1u << 20);
-      } else {
-        snap.reset(new gwa::SnapReader(path));
-      }
-    } else {
-      in = ::open(path, O_RDONLY);
-      if (in < 0) throw std::runtime_error(std::string("cannot open ") + path);
-      struct stat st;
-      if (::fstat(in, &st) == 0 && S_ISREG(st.st_mode)) end = std::min<uint64_t>(end, (uint64_t)st.st_size);
-      if (begin > end) begin = end;
-      if (::lseek(in, (off_t)begin, SEEK_SET) < 0) throw std::runtime_error(std::string("cannot seek in ") + path);
-    }
-    struct stat sb;
-    const off_t pos0 = ::lseek(fd, 0, SEEK_CUR);
-    run.fd = fd;
-    // batches are written at their offsets (pwrite) only to a regular file opened without O_APPEND:
-    // pwrite ignores the offset under O_APPEND (Linux) and would append in completion order
-    const int fl = ::fcntl(fd, F_GETFL);
-    run.seekable = pos0 >= 0 && fl >= 0 && !(fl & O_APPEND) && ::fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
-    run.base = run.seekable ? (uint64_t)pos0 : 0;
-    // chunk size: the whole file when it is smaller than kChunk (plain files; .gz sizes are unknown)
-    uint64_t fileBytes = 0;
-    {
-      struct stat st;
-      if (!gz && ::fstat(in, &st) == 0 && S_ISREG(st.st_mode)) fileBytes = end - begin;
-    }
-    const uint64_t chunk = fileBytes ? std::min<uint64_t>(kChunk, ((fileBytes >> 20) + 1) << 20) : kChunk;
-    const uint64_t reserve = std::min<uint64_t>(kReserve, 2 * chunk);
-    // Pin the read-text buffers this run keeps in flight (read-ahead, the chunk being framed, the
-    // batches in the workers) before it starts -- pinning while batches run stalls their copies in
-    // the runtime (measured: FASTQ -> SAM 8 M reads/s with background pinning, 20-25 M with the
-    // buffers pinned first) -- as many as the file needs, at most a quarter of the available host
-    // memory, kept for later calls.  Beyond them runs use pageable buffers.
-    uint64_t pinnedUsable = 0;
-    // Buffers pinned by an earlier call for a smaller file cannot hold this file's chunks: they are
-    // unpinned, and only the pinned buffers of at least reserve + chunk bytes count.
-    {
-      const uint64_t nbuf = 4 + (uint64_t)p->ix.size() * (uint64_t)p->workersPerDevice;
-      const uint64_t need = fileBytes ? std::min<uint64_t>(nbuf, fileBytes / chunk + 3) : nbuf;
-      const uint64_t avail = memAvailable(), capB = avail ? avail / 4 : (8ull << 30);
-      const uint64_t bufCap = reserve + chunk;
-      uint64_t relN = 0, relB = 0;
-      p->pool.releasePinnedBelow(bufCap, &relN, &relB);
-      p->pinnedBufs -= std::min(p->pinnedBufs, relN);
-      p->pinnedBytes -= std::min(p->pinnedBytes, relB);
-      uint64_t usable = p->pool.countPinned(bufCap);
-      try {
-        while (usable < need && p->pinnedBytes + bufCap <= capB) {
-          p->pool.addPinned(bufCap);
-          ++p->pinnedBufs;
-          ++usable;
-          p->pinnedBytes += bufCap;
-        }
-      } catch (std::exception &) {  // (pinning failed: pageable buffers)
-      }
-      pinnedUsable = usable;
-    }
+    // The stream's IO thread reads the file in chunks into pooled pinned buffers and this thread
+    // frames them into batches of complete records (record_stream.cpp); the workers do the rest.
+    gwa::RecordStream rs(path, begin, end, p->batchReads, [p](size_t cap) { return p->pool.get(cap); });
+    setOutput(run, fd);
+    const uint64_t pinnedUsable = pinReadBuffers(p, {&rs});
     const auto t0 = Clock::now();
-    double readS = 0, frameS = 0;
     run.startFile();
-    // This thread reads the file and frames it into batches of complete records (FASTQ: every
-    // record's header offset, from the '\n' positions found on several threads); the workers do the
-    // rest.  Only full batches leave a chunk unless the file has ended; the rest carries over.
-    // An IO thread reads the file in chunks into pooled pinned buffers, behind `reserve` bytes of
-    // room where this thread puts the records carried over from the previous chunk; this thread frames
-    // each chunk into batches of complete records (FASTQ: every record's header offset) while the IO
-    // thread reads the next.  Only full batches leave a chunk unless the file has ended.
-    const unsigned nth = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
-    struct Chunk {
-      std::shared_ptr<TextBuf> buf;
-      uint64_t got = 0;
-      bool final = false;
-    };
-    std::mutex qmu;
-    std::condition_variable qcv;
-    std::deque<Chunk> q;
-    bool ioDone = false, stop = false;
-    std::string ioErr;
-    std::thread io([&] {
-      try {
-        for (;;) {
-          {
-            std::unique_lock<std::mutex> g(qmu);
-            qcv.wait(g, [&] { return stop || q.size() < 2; });
-            if (stop) break;
-          }
-          Chunk c;
-          c.buf = pool.get(reserve + chunk);
-          const auto r0 = Clock::now();
-          char *dst = c.buf->p + reserve;
-          if (snap) {
-            c.got = snap->read(dst, chunk);
-          } else if (gz) {
-            while (c.got < chunk) {
-              const int r = gzread(f, dst + c.got, (unsigned)(chunk - c.got));
-              if (r < 0) throw std::runtime_error(std::string("read error: ") + path);
-              if (r == 0) break;
-              c.got += (uint64_t)r;
-            }
-          } else {  // four preads at a time (the page cache copies in parallel), up to `end`
-            const off_t at = ::lseek(in, 0, SEEK_CUR);
-            const uint64_t want = std::min<uint64_t>(chunk, end > (uint64_t)at ? end - (uint64_t)at : 0);
-            std::atomic<bool> bad{false};
-            std::vector<std::thread> th;
-            std::vector<uint64_t> gotk(4, 0);
-            auto lo = [&](int k) { return want * (uint64_t)k / 4; };
-            for (int k = 0; k < 4; ++k)
-              th.emplace_back([&, k] {
-                const uint64_t part = lo(k + 1) - lo(k);
-                uint64_t gk = 0;
-                while (gk < part) {
-                  const ssize_t r = ::pread(in, dst + lo(k) + gk, (size_t)(part - gk), at + (off_t)(lo(k) + gk));
-                  if (r < 0) { bad = true; return; }
-                  if (r == 0) break;
-                  gk += (uint64_t)r;
-                }
-                gotk[(size_t)k] = gk;
-              });
-            for (auto &x : th) x.join();
-            if (bad) throw std::runtime_error(std::string("read error: ") + path);
-            // the bytes read are contiguous up to the first short part (end of file)
-            for (int k = 0; k < 4; ++k) {
-              c.got += gotk[(size_t)k];
-              if (gotk[(size_t)k] < lo(k + 1) - lo(k)) break;
-            }
-            ::lseek(in, at + (off_t)c.got, SEEK_SET);
-            if ((uint64_t)at + c.got >= end) c.got = std::min<uint64_t>(c.got, end - (uint64_t)at);
-          }
-          c.final = c.got < chunk || (!gz && (uint64_t)::lseek(in, 0, SEEK_CUR) >= end);
-          const double rs = secs(r0, Clock::now());
-          std::lock_guard<std::mutex> g(qmu);
-          readS += rs;
-          const bool fin = c.final;
-          q.push_back(std::move(c));
-          qcv.notify_all();
-          if (fin) break;
-        }
-      } catch (std::exception &e) {
-        std::lock_guard<std::mutex> g(qmu);
-        ioErr = e.what();
-      }
-      std::lock_guard<std::mutex> g(qmu);
-      ioDone = true;
-      qcv.notify_all();
-    });
-    std::shared_ptr<TextBuf> prev;
-    uint64_t carryFrom = 0, carryLen = 0, id = 0;
-    bool ok = true;
-    std::vector<uint64_t> starts;
-    try {
-      for (;;) {
-        Chunk c;
-        {
-          std::unique_lock<std::mutex> g(qmu);
-          qcv.wait(g, [&] { return !q.empty() || ioDone; });
-          if (q.empty()) {
-            if (!ioErr.empty()) throw std::runtime_error(ioErr);
-            break;
-          }
-          c = std::move(q.front());
-          q.pop_front();
-          qcv.notify_all();
-        }
-        const auto f0 = Clock::now();
-        // the text of this round: the carried records, then the chunk
-        std::shared_ptr<TextBuf> buf = c.buf;
-        uint64_t base = reserve - carryLen;
-        if (carryLen > reserve) {  // more carry than room: one buffer holding both
-          buf = pool.get(carryLen + c.got + 64);
-          memcpy(buf->p + carryLen, c.buf->p + reserve, c.got);
-          base = 0;
-        }
-        if (carryLen) memcpy(buf->p + base, prev->p + carryFrom, carryLen);
-        prev.reset();
-        const char *t = buf->p + base;
-        const uint64_t len = carryLen + c.got;
-        buf->size = base + len;
-        const bool final = c.final;
-        // all complete records of the text: their header offsets (FASTQ) and the end of the last
-        starts.clear();
-        uint64_t nrec = 0, done = 0;
-        bool fast = false;
-        if (fmt == 1 && !final) {  // no '\r', no blank line: record k starts after newline 4k - 1
-          std::vector<uint64_t> cnt(nth);
-          std::vector<char> bl(nth), cr(nth);
-          std::vector<std::thread> th;
-          for (unsigned k = 0; k < nth; ++k)
-            th.emplace_back([&, k] {
-              bool b0, c0;
-              gwa::newlineCount(t, len * k / nth, len * (k + 1) / nth, &cnt[k], &b0, &c0);
-              bl[k] = b0;
-              cr[k] = c0;
-            });
-          for (auto &x : th) x.join();
-          bool clean = len > 0 && t[0] != '\n';
-          uint64_t tot = 0;
-          std::vector<uint64_t> g0(nth);
-          for (unsigned k = 0; k < nth; ++k) {
-            clean = clean && !bl[k] && !cr[k];
-            g0[k] = tot;
-            tot += cnt[k];
-          }
-          if (clean) {
-            fast = true;
-            nrec = tot / 4;
-            starts.resize(nrec + 1);
-            starts[0] = 0;
-            th.clear();
-            for (unsigned k = 0; k < nth; ++k)
-              th.emplace_back([&, k] {
-                gwa::recordStartsFromNewlines(t, len * k / nth, len * (k + 1) / nth, g0[k], starts.data(), nrec + 1);
-              });
-            for (auto &x : th) x.join();
-            done = starts[nrec];  // the start of the first incomplete record
-            starts.resize(nrec);
-          }
-        }
-        if (!fast) done = gwa::frameRecords(t, len, fmt, final, ~0ull, &nrec, fmt == 1 ? &starts : nullptr);
-        frameS += secs(f0, Clock::now());
-        // batches of batchReads records; the records after the last full batch carry over
-        const uint64_t B = p->batchReads;
-        const uint64_t full = final ? (nrec + B - 1) / B : nrec / B;
-        uint64_t pos = 0;
-        if (fmt == 1) {
-          for (uint64_t k = 0; k < full && ok; ++k) {
-            const uint64_t r0i = k * B, r1i = std::min(nrec, r0i + B);
-            Job j;
-            j.id = id++;
-            j.text = buf;
-            j.tb = base + starts[r0i];
-            j.te = base + (r1i < nrec ? starts[r1i] : done);
-            j.format = fmt;
-            j.starts.assign(starts.begin() + (long)r0i, starts.begin() + (long)r1i);
-            const uint64_t s0 = starts[r0i];
-            for (auto &x : j.starts) x -= s0;
-            if (!run.push(std::move(j))) ok = false;
-          }
-          pos = (full * B < nrec) ? starts[full * B] : done;
-        } else {  // FASTA: frame again batch by batch (record starts are not kept)
-          uint64_t left = full == 0 ? 0 : nrec;
-          while (left > 0 && ok) {
-            uint64_t nr = 0;
-            const uint64_t e = pos + gwa::frameRecords(t + pos, len - pos, fmt, final, std::min<uint64_t>(B, left), &nr, nullptr);
-            if (nr == 0) break;
-            if (nr < B && !final) break;
-            Job j;
-            j.id = id++;
-            j.text = buf;
-            j.tb = base + pos;
-            j.te = base + e;
-            j.format = fmt;
-            if (!run.push(std::move(j))) ok = false;
-            pos = e;
-            left -= nr;
-          }
-        }
-        if (!ok || final) break;
-        prev = buf;
-        carryFrom = base + pos;
-        carryLen = len - pos;
-      }
-    } catch (...) {
-      {
-        std::lock_guard<std::mutex> g(qmu);
-        stop = true;
-        qcv.notify_all();
-      }
-      io.join();
-      throw;
+    gwa::RecordSlice s;
+    uint64_t id = 0;
+    while (rs.next(&s)) {
+      Job j;
+      j.id = id++;
+      j.text = std::move(s.buf);
+      j.tb = s.tb;
+      j.te = s.te;
+      j.format = s.format;
+      j.starts = std::move(s.starts);
+      if (!run.push(std::move(j))) break;
     }
-    {
-      std::lock_guard<std::mutex> g(qmu);
-      stop = true;
-      qcv.notify_all();
-    }
-    io.join();
-    q.clear();
-    if (in >= 0) ::close(in);
-    in = -1;
-    run.finishJobs();
-    for (auto &t : run.workers) t.join();
-    run.workers.clear();
-    if (f) gzclose(f);
-    f = nullptr;
-    if (run.failed) throw std::runtime_error(run.err);
-    if (run.seekable) ::lseek(fd, (off_t)(run.base + run.nextOff), SEEK_SET);
-    const uint64_t n = run.fileReads;
-    if (n_reads) *n_reads = n;
-    gwa_pipeline_stats_t &st = p->stats;
-    st = gwa_pipeline_stats_t{};
-    st.reads = n;
-    st.batches = run.fileBatches;
-    st.pinned_bufs = pinnedUsable;
-    st.wall_s = secs(t0, Clock::now());
-    st.read_s = readS;
-    st.frame_s = frameS;
-    for (size_t d = 0; d < p->ix.size() && d < 16; ++d) st.device_kernel_s[d] = run.devBusy[d];
-    st.parse_s = run.parseS;
-    st.setup_s = run.setupS;
-    st.format_s = run.formatS;
-    st.write_s = run.writeS;
-    st.order_wait_s = run.waitS;
+    finishFileRun(p, run, fd, t0, rs.readSeconds(), rs.frameSeconds(), pinnedUsable);
+    if (n_reads) *n_reads = run.fileReads;
     return 0;
   } catch (std::exception &e) {
     run.fail(e.what());
     run.join();
-    if (f) gzclose(f);
-    if (in >= 0) ::close(in);
+    return gwa_fail_message(e.what());
+  }
+}
+
+int gwa_pipeline_align_pair_files(gwa_pipeline_t *p, const char *path1, const char *path2, int32_t min_insert,
+                                  int32_t max_insert, uint32_t flags, int fd, uint64_t *n_pairs) {
+  Run run(p);
+  PairSetup ps;
+  try {
+    checkPairRun(p->cfg, min_insert, max_insert);
+    if (flags & ~(uint32_t)GWA_PAIR_CHECK_NAMES) throw std::runtime_error("gwa_pipeline_align_pair_files: unknown flag");
+    ps.minInsert = min_insert;
+    ps.maxInsert = max_insert;
+    ps.checkNames = (flags & GWA_PAIR_CHECK_NAMES) != 0;
+    ps.label1 = path1;
+    ps.label2 = path2 ? path2 : path1;
+    run.pair = &ps;
+    // The two mate files as zipped record streams, or one interleaved file (record_stream.cpp
+    // PairedRecordStream); both streams draw their buffers from the pipeline's pool.
+    const bool inter = path2 == nullptr;
+    gwa::PairedRecordStream prs(path1, path2, p->batchReads, [p](size_t cap) { return p->pool.get(cap); });
+    setOutput(run, fd);
+    const uint64_t pinnedUsable = pinReadBuffers(p, prs.streams());
+    const auto t0 = Clock::now();
+    run.startFile();
+    gwa::RecordSlice s1, s2;
+    uint64_t id = 0, np = 0;
+    while (prs.next(&s1, &s2, &np)) {
+      Job j;
+      j.id = id++;
+      j.pairs = np;
+      j.text = std::move(s1.buf);
+      j.tb = s1.tb;
+      j.te = s1.te;
+      j.format = s1.format;
+      j.starts = std::move(s1.starts);
+      if (!inter) {
+        j.text2 = std::move(s2.buf);
+        j.tb2 = s2.tb;
+        j.te2 = s2.te;
+        j.format2 = s2.format;
+        j.starts2 = std::move(s2.starts);
+      }
+      if (!run.push(std::move(j))) break;
+    }
+    finishFileRun(p, run, fd, t0, prs.readSeconds(), prs.frameSeconds(), pinnedUsable);
+    if (n_pairs) *n_pairs = run.fileReads / 2;
+    return 0;
+  } catch (std::exception &e) {
+    run.fail(e.what());
+    run.join();
     return gwa_fail_message(e.what());
   }
 }

@@ -1,0 +1,358 @@
+// record_stream.cpp -- the pipeline's file reader and record framer (record_stream.h): host code
+// only, shared by the single-end and the paired-end file entry points of pipeline.cpp.
+#include "record_stream.h"
+
+#include <zlib.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+#include <stdexcept>
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include "snappy_stream.h"
+
+namespace gwa {
+uint64_t frameRecords(const char *t, uint64_t len, int format, bool final, uint64_t maxRec, uint64_t *nRec,
+                      std::vector<uint64_t> *starts);  // reads_io.cpp
+void newlineCount(const char *t, uint64_t a, uint64_t b, uint64_t *count, bool *blank, bool *cr);
+void recordStartsFromNewlines(const char *t, uint64_t a, uint64_t b, uint64_t g0, uint64_t *starts, uint64_t cap);
+
+namespace {
+using Clock = std::chrono::steady_clock;
+double secs(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+
+// read-file chunks (and the room before each for the records carried over from the previous one);
+// a smaller file reads in one chunk of its own size
+constexpr uint64_t kChunk = 256ull << 20, kReserve = 512ull << 20;
+}  // namespace
+
+int compressedKind(const char *path) {
+  const size_t n = strlen(path);
+  if (n > 3 && strcmp(path + n - 3, ".gz") == 0) return 1;
+  if (n > 5 && strcmp(path + n - 5, ".snap") == 0) return 2;
+  return 0;
+}
+
+int formatOf(const char *path) {
+  std::string s(path);
+  if (s.size() > 3 && s.compare(s.size() - 3, 3, ".gz") == 0) s.resize(s.size() - 3);
+  else if (s.size() > 5 && s.compare(s.size() - 5, 5, ".snap") == 0) s.resize(s.size() - 5);
+  auto ends = [&](const char *x) {
+    const size_t n = strlen(x);
+    return s.size() >= n && s.compare(s.size() - n, n, x) == 0;
+  };
+  if (ends(".fa") || ends(".fasta") || ends(".fan")) return 0;
+  if (ends(".fastq") || ends(".fq")) return 1;
+  throw std::runtime_error(std::string("Unsupported file type: ") + path);
+}
+
+struct RecordStream::Source {
+  gzFile f = nullptr;
+  std::unique_ptr<SnapReader> snap;
+  int in = -1;
+  ~Source() {
+    if (f) gzclose(f);
+    if (in >= 0) ::close(in);
+  }
+};
+
+RecordStream::RecordStream(const char *path, uint64_t begin, uint64_t end, uint64_t batchRecords, TextAlloc alloc,
+                           uint64_t chunkBytes)
+    : path_(path), begin_(begin), end_(end), batch_(std::max<uint64_t>(1, batchRecords)), alloc_(std::move(alloc)),
+      src_(new Source()) {
+  fmt_ = formatOf(path);
+  kind_ = compressedKind(path);
+  const bool whole = begin == 0 && end == ~0ull;
+  if (kind_) {
+    if (!whole) throw std::runtime_error(std::string("a byte range needs an uncompressed read file: ") + path);
+    if (kind_ == 1) {
+      src_->f = gzopen(path, "rb");
+      if (!src_->f) throw std::runtime_error(std::string("cannot open ") + path);
+      gzbuffer(src_->f, 1u << 20);
+    } else {
+      src_->snap.reset(new SnapReader(path));
+    }
+  } else {
+    src_->in = ::open(path, O_RDONLY);
+    if (src_->in < 0) throw std::runtime_error(std::string("cannot open ") + path);
+    struct stat st;
+    const bool regular = ::fstat(src_->in, &st) == 0 && S_ISREG(st.st_mode);
+    if (regular) end_ = std::min<uint64_t>(end_, (uint64_t)st.st_size);
+    if (begin_ > end_) begin_ = end_;
+    if (::lseek(src_->in, (off_t)begin_, SEEK_SET) < 0) throw std::runtime_error(std::string("cannot seek in ") + path);
+    // chunk size: the whole file when it is smaller than kChunk (plain files; compressed sizes are unknown)
+    if (regular) fileBytes_ = end_ - begin_;
+  }
+  chunk_ = fileBytes_ ? std::min<uint64_t>(kChunk, ((fileBytes_ >> 20) + 1) << 20) : kChunk;
+  if (chunkBytes) chunk_ = chunkBytes;
+  // GWA_PIPE_CHUNK (tests): chunk size in bytes, so that small files read in many chunks and take the
+  // carry paths
+  if (const char *e = getenv("GWA_PIPE_CHUNK"))
+    if (strtoull(e, nullptr, 10) > 0) chunk_ = strtoull(e, nullptr, 10);
+  reserve_ = std::min<uint64_t>(kReserve, 2 * chunk_);
+}
+
+RecordStream::~RecordStream() { stopIo(); }
+
+void RecordStream::stopIo() {
+  {
+    std::lock_guard<std::mutex> g(qmu_);
+    stop_ = true;
+    qcv_.notify_all();
+  }
+  if (io_.joinable()) io_.join();
+  q_.clear();
+}
+
+double RecordStream::readSeconds() {
+  std::lock_guard<std::mutex> g(qmu_);
+  return readS_;
+}
+
+void RecordStream::ioLoop() {
+  const uint64_t chunk = chunk_, reserve = reserve_, end = end_;
+  const bool gz = kind_ != 0;
+  const int in = src_->in;
+  try {
+    for (;;) {
+      {
+        std::unique_lock<std::mutex> g(qmu_);
+        qcv_.wait(g, [&] { return stop_ || q_.size() < 2; });
+        if (stop_) break;
+      }
+      Chunk c;
+      c.buf = alloc_(reserve + chunk);
+      const auto r0 = Clock::now();
+      char *dst = c.buf->p + reserve;
+      if (src_->snap) {
+        c.got = src_->snap->read(dst, chunk);
+      } else if (gz) {
+        while (c.got < chunk) {
+          const int r = gzread(src_->f, dst + c.got, (unsigned)std::min<uint64_t>(chunk - c.got, 1u << 30));
+          if (r < 0) throw std::runtime_error(std::string("read error: ") + path_);
+          if (r == 0) break;
+          c.got += (uint64_t)r;
+        }
+      } else {  // four preads at a time (the page cache copies in parallel), up to `end`
+        const off_t at = ::lseek(in, 0, SEEK_CUR);
+        const uint64_t want = std::min<uint64_t>(chunk, end > (uint64_t)at ? end - (uint64_t)at : 0);
+        std::atomic<bool> bad{false};
+        std::vector<std::thread> th;
+        std::vector<uint64_t> gotk(4, 0);
+        auto lo = [&](int k) { return want * (uint64_t)k / 4; };
+        for (int k = 0; k < 4; ++k)
+          th.emplace_back([&, k] {
+            const uint64_t part = lo(k + 1) - lo(k);
+            uint64_t gk = 0;
+            while (gk < part) {
+              const ssize_t r = ::pread(in, dst + lo(k) + gk, (size_t)(part - gk), at + (off_t)(lo(k) + gk));
+              if (r < 0) { bad = true; return; }
+              if (r == 0) break;
+              gk += (uint64_t)r;
+            }
+            gotk[(size_t)k] = gk;
+          });
+        for (auto &x : th) x.join();
+        if (bad) throw std::runtime_error(std::string("read error: ") + path_);
+        // the bytes read are contiguous up to the first short part (end of file)
+        for (int k = 0; k < 4; ++k) {
+          c.got += gotk[(size_t)k];
+          if (gotk[(size_t)k] < lo(k + 1) - lo(k)) break;
+        }
+        ::lseek(in, at + (off_t)c.got, SEEK_SET);
+        if ((uint64_t)at + c.got >= end) c.got = std::min<uint64_t>(c.got, end - (uint64_t)at);
+      }
+      c.final = c.got < chunk || (!gz && (uint64_t)::lseek(in, 0, SEEK_CUR) >= end);
+      const double rs = secs(r0, Clock::now());
+      std::lock_guard<std::mutex> g(qmu_);
+      readS_ += rs;
+      const bool fin = c.final;
+      q_.push_back(std::move(c));
+      qcv_.notify_all();
+      if (fin) break;
+    }
+  } catch (std::exception &e) {
+    std::lock_guard<std::mutex> g(qmu_);
+    ioErr_ = e.what();
+  }
+  std::lock_guard<std::mutex> g(qmu_);
+  ioDone_ = true;
+  qcv_.notify_all();
+}
+
+// Frame the next chunk (behind the records carried over) into ready_; false when the file has ended.
+bool RecordStream::frameNextChunk() {
+  Chunk c;
+  {
+    std::unique_lock<std::mutex> g(qmu_);
+    qcv_.wait(g, [&] { return !q_.empty() || ioDone_; });
+    if (q_.empty()) {
+      if (!ioErr_.empty()) throw std::runtime_error(ioErr_);
+      return false;
+    }
+    c = std::move(q_.front());
+    q_.pop_front();
+    qcv_.notify_all();
+  }
+  const auto f0 = Clock::now();
+  const uint64_t reserve = reserve_;
+  const int fmt = fmt_;
+  // the text of this round: the carried records, then the chunk
+  std::shared_ptr<TextBuf> buf = c.buf;
+  uint64_t base = reserve - std::min(reserve, carryLen_);
+  if (carryLen_ > reserve) {  // more carry than room: one buffer holding both
+    buf = alloc_(carryLen_ + c.got + 64);
+    memcpy(buf->p + carryLen_, c.buf->p + reserve, c.got);
+    base = 0;
+  }
+  if (carryLen_) memcpy(buf->p + base, prev_->p + carryFrom_, carryLen_);
+  prev_.reset();
+  const char *t = buf->p + base;
+  const uint64_t len = carryLen_ + c.got;
+  buf->size = base + len;
+  const bool final = c.final;
+  // all complete records of the text: their header offsets (FASTQ) and the end of the last
+  std::vector<uint64_t> &starts = starts_;
+  starts.clear();
+  uint64_t nrec = 0, done = 0;
+  bool fast = false;
+  const unsigned nth = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
+  if (fmt == 1 && !final) {  // no '\r', no blank line: record k starts after newline 4k - 1
+    std::vector<uint64_t> cnt(nth);
+    std::vector<char> bl(nth), cr(nth);
+    std::vector<std::thread> th;
+    for (unsigned k = 0; k < nth; ++k)
+      th.emplace_back([&, k] {
+        bool b0, c0;
+        newlineCount(t, len * k / nth, len * (k + 1) / nth, &cnt[k], &b0, &c0);
+        bl[k] = b0;
+        cr[k] = c0;
+      });
+    for (auto &x : th) x.join();
+    bool clean = len > 0 && t[0] != '\n';
+    uint64_t tot = 0;
+    std::vector<uint64_t> g0(nth);
+    for (unsigned k = 0; k < nth; ++k) {
+      clean = clean && !bl[k] && !cr[k];
+      g0[k] = tot;
+      tot += cnt[k];
+    }
+    if (clean) {
+      fast = true;
+      nrec = tot / 4;
+      starts.resize(nrec + 1);
+      starts[0] = 0;
+      th.clear();
+      for (unsigned k = 0; k < nth; ++k)
+        th.emplace_back([&, k] {
+          recordStartsFromNewlines(t, len * k / nth, len * (k + 1) / nth, g0[k], starts.data(), nrec + 1);
+        });
+      for (auto &x : th) x.join();
+      done = starts[nrec];  // the start of the first incomplete record
+      starts.resize(nrec);
+    }
+  }
+  if (!fast) done = frameRecords(t, len, fmt, final, ~0ull, &nrec, fmt == 1 ? &starts : nullptr);
+  // slices of batch_ records; the records after the last full slice carry over
+  const uint64_t B = batch_;
+  const uint64_t full = final ? (nrec + B - 1) / B : nrec / B;
+  uint64_t pos = 0;
+  if (fmt == 1) {
+    for (uint64_t k = 0; k < full; ++k) {
+      const uint64_t r0i = k * B, r1i = std::min(nrec, r0i + B);
+      RecordSlice s;
+      s.buf = buf;
+      s.tb = base + starts[r0i];
+      s.te = base + (r1i < nrec ? starts[r1i] : done);
+      s.n = r1i - r0i;
+      s.format = fmt;
+      s.starts.assign(starts.begin() + (long)r0i, starts.begin() + (long)r1i);
+      const uint64_t s0 = starts[r0i];
+      for (auto &x : s.starts) x -= s0;
+      ready_.push_back(std::move(s));
+    }
+    pos = (full * B < nrec) ? starts[full * B] : done;
+  } else {  // FASTA: frame again slice by slice (record starts are not kept)
+    uint64_t left = full == 0 ? 0 : nrec;
+    while (left > 0) {
+      uint64_t nr = 0;
+      const uint64_t e = pos + frameRecords(t + pos, len - pos, fmt, final, std::min<uint64_t>(B, left), &nr, nullptr);
+      if (nr == 0) break;
+      if (nr < B && !final) break;
+      RecordSlice s;
+      s.buf = buf;
+      s.tb = base + pos;
+      s.te = base + e;
+      s.n = nr;
+      s.format = fmt;
+      ready_.push_back(std::move(s));
+      pos = e;
+      left -= nr;
+    }
+  }
+  frameS_ += secs(f0, Clock::now());
+  if (final) {
+    ended_ = true;
+  } else {
+    prev_ = buf;
+    carryFrom_ = base + pos;
+    carryLen_ = len - pos;
+  }
+  return true;
+}
+
+bool RecordStream::next(RecordSlice *out) {
+  if (!started_) {
+    started_ = true;
+    io_ = std::thread(&RecordStream::ioLoop, this);
+  }
+  while (ready_.empty()) {
+    if (ended_ || !frameNextChunk()) {
+      ended_ = true;
+      return false;
+    }
+  }
+  *out = std::move(ready_.front());
+  ready_.pop_front();
+  return true;
+}
+
+PairedRecordStream::PairedRecordStream(const char *path1, const char *path2, uint64_t batchPairs, TextAlloc alloc) {
+  const uint64_t B = std::max<uint64_t>(1, batchPairs);
+  a_.reset(new RecordStream(path1, 0, ~0ull, path2 ? B : 2 * B, alloc));
+  if (path2) b_.reset(new RecordStream(path2, 0, ~0ull, B, alloc));
+}
+
+bool PairedRecordStream::next(RecordSlice *m1, RecordSlice *m2, uint64_t *pairs) {
+  const bool h1 = a_->next(m1);
+  if (!b_) {
+    if (!h1) return false;
+    if (m1->n % 2) throw std::runtime_error("the interleaved file holds an odd number of reads: " + a_->path());
+    *m2 = RecordSlice();
+    *pairs = m1->n / 2;
+    return true;
+  }
+  const bool h2 = b_->next(m2);
+  if (!h1 && !h2) return false;
+  // every slice but a stream's last holds exactly the batch size, so unequal files show here: as
+  // slices of different sizes, or as one stream ending a slice before the other
+  if (!h1 || !h2 || m1->n != m2->n) throw std::runtime_error("the mate files hold different numbers of reads");
+  *pairs = m1->n;
+  return true;
+}
+
+std::vector<RecordStream *> PairedRecordStream::streams() {
+  std::vector<RecordStream *> v{a_.get()};
+  if (b_) v.push_back(b_.get());
+  return v;
+}
+
+double PairedRecordStream::readSeconds() { return a_->readSeconds() + (b_ ? b_->readSeconds() : 0.0); }
+double PairedRecordStream::frameSeconds() const { return a_->frameSeconds() + (b_ ? b_->frameSeconds() : 0.0); }
+
+}  // namespace gwa

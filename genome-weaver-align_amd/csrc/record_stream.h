@@ -1,0 +1,124 @@
+// record_stream.h -- a read file as a stream of slices of complete records (record_stream.cpp).
+//
+// Host code only (no HIP): the buffers come from an allocator the caller passes in, so the pipeline
+// hands out its pooled pinned buffers and a stand-alone program plain malloc'd ones.
+#pragma once
+#include <condition_variable>
+#include <cstdint>
+#include <deque>
+#include <functional>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+namespace gwa {
+
+// A buffer of read-file text (pipeline.cpp BufPool owns and recycles them).
+struct TextBuf {
+  char *p = nullptr;
+  size_t cap = 0, size = 0;
+  bool pinned = false;
+  const char *data() const { return p; }
+};
+
+// a buffer of at least `cap` bytes; the stream drops its reference once every slice cut from the
+// buffer has been handed out
+using TextAlloc = std::function<std::shared_ptr<TextBuf>(size_t cap)>;
+
+// 1: gzip (.gz), 2: snappy-java (.snap, R/ReadReaderFactory.java:130-139), 0: plain
+int compressedKind(const char *path);
+// 0: FASTA (.fa .fasta .fan), 1: FASTQ (.fastq .fq), below an optional .gz / .snap; throws otherwise
+int formatOf(const char *path);
+
+// `n` complete records: the bytes [tb, te) of buf.  FASTQ: starts[k] = record k's header line,
+// relative to tb (FASTA records are multi-line and parsed on the host, so their starts are not kept).
+struct RecordSlice {
+  std::shared_ptr<TextBuf> buf;
+  uint64_t tb = 0, te = 0, n = 0;
+  int format = 1;
+  std::vector<uint64_t> starts;
+};
+
+// The file's records in order, in slices of exactly batchRecords records (the last one may be
+// shorter).  An IO thread (started by the first next()) reads -- and decompresses -- the file in
+// chunks into buffers from `alloc`, behind `reserve` bytes of room where the records carried over
+// from the previous chunk are put; next() frames each chunk while the IO thread reads the following
+// one.  Only full slices leave a chunk unless the file has ended; the rest carries over.
+class RecordStream {
+ public:
+  // [begin, end): a byte range of a plain file that starts at a record (0, ~0: the whole file; a
+  // compressed file takes no other).  chunkBytes = 0: 256 MB, or the file's size when it is smaller
+  // (GWA_PIPE_CHUNK, a test knob, overrides both).
+  RecordStream(const char *path, uint64_t begin, uint64_t end, uint64_t batchRecords, TextAlloc alloc,
+               uint64_t chunkBytes = 0);
+  ~RecordStream();
+  RecordStream(const RecordStream &) = delete;
+  RecordStream &operator=(const RecordStream &) = delete;
+
+  // the next slice; false at the end of the file.  Throws on a read error.
+  bool next(RecordSlice *out);
+
+  int format() const { return fmt_; }
+  const std::string &path() const { return path_; }
+  uint64_t chunk() const { return chunk_; }
+  uint64_t reserve() const { return reserve_; }
+  uint64_t bufBytes() const { return reserve_ + chunk_; }  // what the IO thread asks `alloc` for
+  uint64_t fileBytes() const { return fileBytes_; }        // 0 = unknown (compressed, or not a regular file)
+  double readSeconds();
+  double frameSeconds() const { return frameS_; }
+
+ private:
+  struct Chunk {
+    std::shared_ptr<TextBuf> buf;
+    uint64_t got = 0;
+    bool final = false;
+  };
+  struct Source;  // the open file (plain descriptor, gzFile or SnapReader)
+  void ioLoop();
+  void stopIo();
+  bool frameNextChunk();
+
+  std::string path_;
+  int fmt_ = 1, kind_ = 0;
+  uint64_t begin_ = 0, end_ = ~0ull, batch_ = 1, chunk_ = 0, reserve_ = 0, fileBytes_ = 0;
+  TextAlloc alloc_;
+  std::unique_ptr<Source> src_;
+  // IO thread and its queue (at most two chunks read ahead)
+  std::thread io_;
+  std::mutex qmu_;
+  std::condition_variable qcv_;
+  std::deque<Chunk> q_;
+  bool started_ = false, ioDone_ = false, stop_ = false;
+  std::string ioErr_;
+  double readS_ = 0, frameS_ = 0;
+  // framing state: the records carried over, the slices of the current chunk not yet handed out
+  std::shared_ptr<TextBuf> prev_;
+  uint64_t carryFrom_ = 0, carryLen_ = 0;
+  bool ended_ = false;
+  std::deque<RecordSlice> ready_;
+  std::vector<uint64_t> starts_;
+};
+
+// Paired-end input: two record streams, slice k of the one zipped with slice k of the other (the
+// files differ in bytes per record, so each stream frames and carries on its own); or, with path2 ==
+// nullptr, one stream of an interleaved file at twice the batch size (records 2i and 2i + 1 form pair
+// i).  next() throws when the mate files hold different numbers of records -- either being the
+// longer, by any count -- and when an interleaved file holds an odd number.
+class PairedRecordStream {
+ public:
+  PairedRecordStream(const char *path1, const char *path2, uint64_t batchPairs, TextAlloc alloc);
+  // the next `*pairs` pairs: mate 1 in *m1 and mate 2 in *m2, or both alternating in *m1 (interleaved;
+  // *m2 is left empty); false at the end of the input
+  bool next(RecordSlice *m1, RecordSlice *m2, uint64_t *pairs);
+  bool interleaved() const { return !b_; }
+  std::vector<RecordStream *> streams();
+  double readSeconds();
+  double frameSeconds() const;
+
+ private:
+  std::unique_ptr<RecordStream> a_, b_;
+};
+
+}  // namespace gwa

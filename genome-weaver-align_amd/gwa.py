@@ -103,7 +103,7 @@ EXPORTS = ["gwa_config_default", "gwa_last_error", "gwa_device_count", "gwa_inde
            "gwa_batch_read_counters", "gwa_batch_results_range", "gwa_results_records", "gwa_batch_results_select", "gwa_batch_format",
            "gwa_batch_sam_copy",
            "gwa_pipeline_open", "gwa_pipeline_align", "gwa_pipeline_align_file", "gwa_pipeline_align_file_range",
-           "gwa_reads_shard_range", "gwa_pipeline_stats",
+           "gwa_pipeline_align_pair_files", "gwa_pipeline_align_pairs", "gwa_reads_shard_range", "gwa_pipeline_stats",
            "gwa_pipeline_close", "gwa_reads_parse", "gwa_reads_free", "gwa_snappy_decompress"]
 
 
@@ -149,6 +149,10 @@ def lib():
         L.gwa_pipeline_align.argtypes = [V, P(_Reads), P(_Results)]
         L.gwa_pipeline_align_file.argtypes = [V, ctypes.c_char_p, I, P(U64)]
         L.gwa_pipeline_align_file_range.argtypes = [V, ctypes.c_char_p, I, U64, U64, P(U64)]
+        if hasattr(L, "gwa_pipeline_align_pair_files"):  # (older libraries in A/B runs lack them)
+            L.gwa_pipeline_align_pair_files.argtypes = [V, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32, ctypes.c_int32,
+                                                        ctypes.c_uint32, I, P(U64)]
+            L.gwa_pipeline_align_pairs.argtypes = [V, P(_Reads), P(_Reads), ctypes.c_int32, ctypes.c_int32, P(_Results)]
         L.gwa_reads_shard_range.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, P(U64), P(U64)]
         L.gwa_pipeline_stats.argtypes = [V, P(PipelineStats)]
         L.gwa_pipeline_close.argtypes = [V]
@@ -457,6 +461,9 @@ def aligner(fmIndex, config):
     raise GwaError("%s mode is not supported" % config.strategy)
 
 
+PAIR_CHECK_NAMES = 1  # include/gwa.h GWA_PAIR_CHECK_NAMES
+
+
 class Pipeline:
     """Multi-device driver (include/gwa.h gwa_pipeline_*): read batches dealt to several index replicas
     (one per GPU), SAM in input order.  indexes: FMIndexOnGenome handles, one per device."""
@@ -494,6 +501,27 @@ class Pipeline:
             b, e = shard_range(path, *shard)
             _check(lib().gwa_pipeline_align_file_range(self.h, path.encode(), fd, b, e, ctypes.byref(n)))
         return n.value
+
+    def align_pair_files(self, path1, path2, fd, insert=(210, 390), check_names=False):
+        """Stream two mate files (path2 None: one interleaved file) through the devices; two SAM lines per
+        pair to file descriptor fd, in pair order (gwa_pipeline_align_pair_files).  Returns the pairs.
+        check_names: fail on the first pair whose mate names differ (a trailing /1 or /2 apart)."""
+        n = ctypes.c_uint64()
+        _check(lib().gwa_pipeline_align_pair_files(self.h, path1.encode(), path2.encode() if path2 is not None else None,
+                                                   insert[0], insert[1], PAIR_CHECK_NAMES if check_names else 0, fd,
+                                                   ctypes.byref(n)))
+        return n.value
+
+    def align_pairs(self, mates1, mates2, insert=(210, 390)):
+        """mates: lists of (name, seq, qual-or-None) -> SAM text (no header), pair order."""
+        keep = []
+        return self.align_pair_structs(_reads_struct(mates1, keep), _reads_struct(mates2, keep), insert)
+
+    def align_pair_structs(self, r1, r2, insert=(210, 390)):
+        res = _Results()
+        _check(lib().gwa_pipeline_align_pairs(self.h, ctypes.byref(r1), ctypes.byref(r2), insert[0], insert[1],
+                                              ctypes.byref(res)))
+        return _take_results(res)[0]
 
     def stats(self):
         st = PipelineStats()

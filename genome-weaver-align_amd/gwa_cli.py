@@ -5,6 +5,9 @@ A/AlignmentConfig.java:40-72, A/AlignmentScoreConfig.java:37-77).
   python genome-weaver-align_amd/gwa_cli.py align -r ref.fa [-q SEQ | reads.fq[.gz|.snap] | reads.fa[.gz|.snap]]
          [-k 0.1] [-m bsf|sf|bd|bwa] [-R besthit|allhits|topL] [-L 5] [-g 1] [-e 4] [-s 1] [-M 1] [-N 3]
          [-G 11] [-E 4] [-S 11] [-P 5] [-W 31] [--silent] [--devices 0,1,..] [--batch 1048576]
+  python genome-weaver-align_amd/gwa_cli.py align -r ref.fa mates_1.fq[.gz|.snap] mates_2.fq[.gz|.snap]
+         [--insert-min 210] [--insert-max 390] [--check-mate-names]       (paired-end, two SAM lines per pair)
+  python genome-weaver-align_amd/gwa_cli.py align -r ref.fa --interleaved pairs.fq   (mates alternating in one file)
 
 Writes SAM to stdout: the `@SQ` header (SequenceBoundary.toSAMHeader, A/SequenceBoundary.java:81-87)
 then one record per read in input order, as SAMOutput does (A/SAMOutput.java:56-82).  Read files go
@@ -13,6 +16,12 @@ replica per GPU in --devices, SAM written back in input order.  Like the referen
 files its `bwt` command wrote next to the FASTA (A/FMIndexOnGenome.java:60-86, A/BWTFiles.java:40-80),
 `align -r ref.fa` loads `ref.fa.gwa.idx` when `bwt` made one, and otherwise builds the index on the GPU
 from the FASTA.
+
+Two read files (or one with --interleaved) are paired-end input: mate i of the first file with mate i
+of the second, two SAM lines per pair, streamed through the same pipeline on every device of
+--devices (gwa_pipeline_align_pair_files; --batch then counts pairs).  The reference prints only the
+header for two read files: its paired reader is a stub (R/ReadReaderFactory.java:60-84); the pairing
+rules are this build's own (include/gwa.h gwa_batch_create_pairs), -m bsf only.
 
 Read input follows ReadReaderFactory.createReader (R/ReadReaderFactory.java:126-151): `.fa`,
 `.fasta`, `.fan`, `.fastq`, `.fq`, optionally `.gz` or `.snap` (snappy-java stream); `-q` aligns one query named "read" with no
@@ -37,13 +46,6 @@ def _open(path):
         with open(path, "rb") as f:
             return io.TextIOWrapper(io.BytesIO(gwa.snappy_decompress(f.read())))
     return gzip.open(path, "rt") if path.endswith(".gz") else open(path, "rt")
-
-
-def _open_bytes(path):
-    if path.endswith(".snap"):
-        with open(path, "rb") as f:
-            return io.BytesIO(gwa.snappy_decompress(f.read()))
-    return gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")
 
 
 def _kind(path):
@@ -139,6 +141,10 @@ def build_parser():
     a.add_argument("--insert-max", type=int, default=390,
                    help="paired-end: largest template length of a proper pair (mate rescue needs max - min + read "
                         "length + 2k <= 320 bases; wider ranges pair without rescue)")
+    a.add_argument("--interleaved", action="store_true",
+                   help="paired-end: the one read file holds both mates, records 2i and 2i + 1 forming pair i")
+    a.add_argument("--check-mate-names", action="store_true",
+                   help="paired-end: fail on the first pair whose mate names differ (one trailing /1 or /2 apart)")
     a.add_argument("--sync", default=None, metavar="DIR:N",
                    help="timing runs of N processes (--shard): after the warm passes, wait until all N have written a "
                         "ready file into DIR, so their timed passes run at the same time; --timing then also prints "
@@ -221,10 +227,17 @@ def align(ns, out=sys.stdout):
         raise gwa.GwaError("no query is given")
     if ns.query is None and len(ns.readFiles) not in (1, 2):
         raise gwa.GwaError("give one read file (single-end) or two mate files (paired-end)")
+    if ns.interleaved and (ns.query is not None or len(ns.readFiles) != 1):
+        raise gwa.GwaError("--interleaved takes one read file holding both mates of every pair")
+    paired = ns.query is None and (len(ns.readFiles) == 2 or ns.interleaved)
+    if ns.check_mate_names and not paired:
+        raise gwa.GwaError("--check-mate-names needs paired-end input (two mate files, or --interleaved)")
     cfg = config_of(ns)
     shard = shard_of(ns)
-    if shard is not None and (ns.query is not None or len(ns.readFiles) != 1):
+    if shard is not None and (ns.query is not None or paired):
         raise gwa.GwaError("--shard splits one single-end read file")
+    if paired and cfg.strategy.lower() != "bsf":
+        raise gwa.GwaError("paired-end alignment runs -m bsf")
     if ns.query is None:
         for f in ns.readFiles:
             _kind(f)  # unsupported suffixes fail before the index is built
@@ -239,12 +252,19 @@ def align(ns, out=sys.stdout):
         w(fms[0].samHeader())
     n = 0
     t_open = 0.0
+    mono0 = None
+
+    def run_file(pipe, fd):
+        """one pass over the read file(s) into fd; reads (single-end) or pairs (paired-end) aligned"""
+        if paired:
+            return pipe.align_pair_files(ns.readFiles[0], ns.readFiles[1] if len(ns.readFiles) == 2 else None, fd,
+                                         (ns.insert_min, ns.insert_max), ns.check_mate_names)
+        return pipe.align_file(ns.readFiles[0], fd, shard=shard)
+
     try:
         if ns.query is not None:
             w(gwa.aligner(fms[0], cfg).align_batch([("read", ns.query, None)]))
             n = 1
-        elif len(ns.readFiles) == 2:
-            n = align_pairs(ns, fms[0], cfg, w)
         else:
             out.flush()
             tp = time.perf_counter()
@@ -255,7 +275,7 @@ def align(ns, out=sys.stdout):
                 # device caches and the page cache warm), then the timed pass that writes the SAM
                 for _ in range(max(0, ns.warm_passes - 1)):
                     with open(os.devnull, "wb") as dn:
-                        pipe.align_file(ns.readFiles[0], dn.fileno(), shard=shard)
+                        run_file(pipe, dn.fileno())
                 if ns.sync:
                     sync_wait(ns.sync)
                 if ns.warm_passes > 1 or ns.sync:
@@ -263,14 +283,14 @@ def align(ns, out=sys.stdout):
                 mono0 = time.monotonic_ns()
                 if ns.silent:
                     with open(os.devnull, "wb") as dn:
-                        n = pipe.align_file(ns.readFiles[0], dn.fileno(), shard=shard)
+                        n = run_file(pipe, dn.fileno())
                 else:
                     try:
                         fd = out.fileno()
                     except (AttributeError, io.UnsupportedOperation):
                         fd = None
                     if fd is not None:
-                        n = pipe.align_file(ns.readFiles[0], fd, shard=shard)
+                        n = run_file(pipe, fd)
                         if ns.timing:
                             st = pipe.stats()
                             print("[gwa] pipeline %.2fs: read %.2fs, frame %.2fs; summed over %d worker threads: parse %.2fs, "
@@ -280,48 +300,26 @@ def align(ns, out=sys.stdout):
                                      st.format_s, st.write_s, st.order_wait_s), file=sys.stderr)
                     else:  # an in-memory stream (tests): through a temporary file
                         with tempfile.TemporaryFile() as tf:
-                            n = pipe.align_file(ns.readFiles[0], tf.fileno(), shard=shard)
+                            n = run_file(pipe, tf.fileno())
                             tf.seek(0)
                             out.write(tf.read().decode())
             finally:
                 t2 = time.perf_counter()  # (the SAM is written; unpinning the buffers is teardown)
-                if ns.timing and ns.sync:
+                if ns.timing and ns.sync and mono0 is not None:  # (None: a warm pass or the sync wait failed)
                     print("[gwa] timed pass monotonic_ns %d %d" % (mono0, time.monotonic_ns()), file=sys.stderr)
                 pipe.close()
-        if ns.query is not None or len(ns.readFiles) == 2:
+        if ns.query is not None:
             t2 = time.perf_counter()
     finally:
         for fm in fms:
             fm.close()
     if ns.timing:
+        nr = 2 * n if paired else n  # (reads per second count mates)
         print("[gwa] index load %.2fs (%d device(s)); align (read file -> SAM, index load excluded) %.2fs: %.0f reads/s; "
               "of which pipeline open (pinning host buffers) %.2fs, after it %.0f reads/s"
-              % (t1 - t0, len(devices), t2 - t1, n / max(t2 - t1, 1e-9), t_open, n / max(t2 - t1 - t_open, 1e-9)),
+              % (t1 - t0, len(devices), t2 - t1, nr / max(t2 - t1, 1e-9), t_open, nr / max(t2 - t1 - t_open, 1e-9)),
               file=sys.stderr)
     return n
-
-
-def align_pairs(ns, fm, cfg, w):
-    """Paired-end: mate i of the first file with mate i of the second (gwa_align_pairs, one GPU),
-    two SAM lines per pair.  The reference prints only the header for two read files: its paired
-    reader is a stub (R/ReadReaderFactory.java:60-84); the pairing rules are this build's own
-    (include/gwa.h gwa_batch_create_pairs)."""
-    if cfg.strategy.lower() != "bsf":
-        raise gwa.GwaError("paired-end alignment runs -m bsf")
-    pe = gwa.PairedEndAligner(fm, cfg, ns.insert_min, ns.insert_max)
-    with _open_bytes(ns.readFiles[0]) as f1, _open_bytes(ns.readFiles[1]) as f2:
-        p1 = gwa.ParsedReads(f1.read(), _kind(ns.readFiles[0]))
-        p2 = gwa.ParsedReads(f2.read(), _kind(ns.readFiles[1]))
-    try:
-        if p1.n != p2.n:
-            raise gwa.GwaError("the mate files hold %d and %d reads" % (p1.n, p2.n))
-        for i in range(0, p1.n, ns.batch):
-            c = min(ns.batch, p1.n - i)
-            w(pe.align_pair_structs(p1.slice(i, c), p2.slice(i, c)))
-        return p1.n
-    finally:
-        p1.close()
-        p2.close()
 
 
 def bwt(ns):

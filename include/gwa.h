@@ -241,6 +241,30 @@ int gwa_pipeline_align_file(gwa_pipeline_t *p, const char *path, int fd, uint64_
  * (gwa_reads_shard_range gives such ranges). */
 int gwa_pipeline_align_file_range(gwa_pipeline_t *p, const char *path, int fd, uint64_t begin, uint64_t end,
                                   uint64_t *n_reads);
+/* Paired-end read files streamed through the devices like gwa_pipeline_align_file: mate i of path1
+ * pairs with mate i of path2; path2 == NULL means path1 is interleaved (records 2i and 2i + 1 form
+ * pair i).  Each file may be FASTA or FASTQ, plain, .gz or .snap, independently of the other.  Two
+ * SAM lines per pair (no header) are written to fd in pair order under the output rules above, byte
+ * for byte what gwa_align_pairs gives for the same pairs; *n_pairs = pairs aligned, and
+ * gwa_pipeline_stats_t.reads counts mates (two per pair).  batch_reads of gwa_pipeline_open counts
+ * pairs here.  FASTQ mates go to HBM as text, both slices into one allocation, and are parsed there;
+ * a batch with a FASTA mate is parsed on the host.  Host memory does not grow with the files: at most
+ * `depth` pair batches are in flight, and the two files share the pinned-buffer budget of one.
+ * flags: GWA_PAIR_CHECK_NAMES compares the mates' names (the parser's first whitespace-delimited
+ * token, one trailing "/1" or "/2" removed from each; QNAME in the SAM is never altered) on the
+ * device, and a differing pair fails the run with the lowest such pair index and both names.
+ * Errors: -m sf and a bad insert range (as gwa_batch_create_pairs); mate files with different record
+ * counts ("the mate files hold different numbers of reads"); an interleaved file with an odd record
+ * count; a malformed record (the message starts with the file's name).  What was written to fd before
+ * an error is unspecified. */
+#define GWA_PAIR_CHECK_NAMES 1u
+int gwa_pipeline_align_pair_files(gwa_pipeline_t *p, const char *path1, const char *path2, int32_t min_insert,
+                                  int32_t max_insert, uint32_t flags, int fd, uint64_t *n_pairs);
+/* The in-memory counterpart (as gwa_pipeline_align is of align_file): pairs of any number of mates,
+ * dealt to the handles in batches of batch_reads pairs; results as gwa_align_pairs gives them
+ * (paired = 1, n_reads = pairs, two lines per pair). */
+int gwa_pipeline_align_pairs(gwa_pipeline_t *p, const gwa_reads_t *mate1, const gwa_reads_t *mate2, int32_t min_insert,
+                             int32_t max_insert, gwa_results_t *out);
 /* One process per GPU (C3; the reference's one read loop, A/Align.java:174-196, split by reads): the
  * byte range [*begin, *end) of shard `shard` of `nshards` contiguous shards of a plain FASTQ / FASTA
  * file, cut at record starts, so that the shards' SAM files concatenated in shard order equal a
