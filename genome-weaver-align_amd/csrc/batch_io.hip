@@ -283,10 +283,15 @@ __device__ __forceinline__ int samUnit(SamOut &o, const SamText &t, uint32_t r, 
   return samRead(o, t, r, oh[r], hits, cig);
 }
 
+// Both passes exist in two instances: TAGS = false is the default output's code, with the optional tags
+// (SamText::tags: MD:Z) compiled out; TAGS = true formats them (the lane walks its records' reference
+// windows, sam_core.h mdEmit).
+template <bool TAGS>
 __global__ void __launch_bounds__(256) samLenKernel(SamText t, const OutHeader *__restrict__ oh, const OutHit *__restrict__ hits,
                                                     const uint16_t *__restrict__ cig, const uint32_t *__restrict__ idx,
                                                     uint32_t first, uint32_t n, uint64_t *__restrict__ len,
                                                     uint32_t *__restrict__ err, PairSpec ps) {
+  if (!TAGS) t.tags = 0;
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j > n) return;
   if (j == n) {  // the scan's total
@@ -458,11 +463,13 @@ constexpr uint32_t kSamWg = 64;
 // (samServeFields).  A range larger than the staging buffer (many reported lines) is written
 // directly to HBM by its lanes.  `out` is only ever written (it may be pinned host memory).
 // Dynamic LDS: cap descriptors of 12 B, the counter, the stage of stageBytes.
+template <bool TAGS>
 __global__ void __launch_bounds__(kSamWg) samWriteKernel(SamText t, const OutHeader *__restrict__ oh, const OutHit *__restrict__ hits,
                                                      const uint16_t *__restrict__ cig, const uint32_t *__restrict__ idx,
                                                      uint32_t first, uint32_t n, const uint64_t *__restrict__ off,
                                                      char *__restrict__ out, PairSpec ps, uint32_t stageBytes, uint32_t cap,
                                                      uint32_t lshift) {
+  if (!TAGS) t.tags = 0;
   extern __shared__ u32x4 samLds[];
   SamField *fields = reinterpret_cast<SamField *>(samLds);
   const uint32_t descBytes = (cap * (uint32_t)sizeof(SamField) + 4 + 15) & ~15u;
@@ -508,7 +515,10 @@ void launchSamFormat(const SamText &t, const OutHeader *oh, const OutHit *hits, 
                      uint32_t *err, char *out, int pass, hipStream_t s, const PairSpec &ps, uint64_t totalBytes) {
   const dim3 grid((n + 1 + 255) / 256);
   if (pass == 0) {
-    hipLaunchKernelGGL(samLenKernel, grid, dim3(256), 0, s, t, oh, hits, cig, idx, first, n, len, err, ps);
+    if (t.tags)
+      hipLaunchKernelGGL(samLenKernel<true>, grid, dim3(256), 0, s, t, oh, hits, cig, idx, first, n, len, err, ps);
+    else
+      hipLaunchKernelGGL(samLenKernel<false>, grid, dim3(256), 0, s, t, oh, hits, cig, idx, first, n, len, err, ps);
     FCHK(hipGetLastError());
   } else if (pass == 1) {  // exclusive scan of n + 1 lengths: off[n] = total bytes
     FCHK(rocprim::exclusive_scan(scanTmp, *scanTmpBytes, len, off, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
@@ -539,8 +549,12 @@ void launchSamFormat(const SamText &t, const OutHeader *oh, const OutHit *hits, 
     uint32_t lshift = 2;
     while (lshift < 6 && (1u << lshift) < fieldItems) ++lshift;
     const uint32_t lds = descBytes + stage;
-    hipLaunchKernelGGL(samWriteKernel, grid2, dim3(wg), lds, s, t, oh, hits, cig, idx, first, n, off, out, ps, stage, cap,
-                       lshift);
+    if (t.tags)
+      hipLaunchKernelGGL(samWriteKernel<true>, grid2, dim3(wg), lds, s, t, oh, hits, cig, idx, first, n, off, out, ps, stage,
+                         cap, lshift);
+    else
+      hipLaunchKernelGGL(samWriteKernel<false>, grid2, dim3(wg), lds, s, t, oh, hits, cig, idx, first, n, off, out, ps, stage,
+                         cap, lshift);
     FCHK(hipGetLastError());
   }
 }

@@ -187,6 +187,18 @@ int fail(const std::string &m) {
 // error path shared with reads_io.cpp (sets gwa_last_error)
 extern "C" int gwa_fail_message(const char *msg) { return fail(msg); }
 
+namespace gwa {
+// gwa_config_t.sam_tags: only defined bits (every batch set-up and gwa_pipeline_open)
+void checkSamTags(uint32_t tags) {
+  if (tags & ~(uint32_t)GWA_SAM_TAG_MD) {
+    char buf[96];
+    snprintf(buf, sizeof buf, "gwa_config_t.sam_tags: unknown bits 0x%x (defined: GWA_SAM_TAG_MD = 1)",
+             tags & ~(uint32_t)GWA_SAM_TAG_MD);
+    throw std::runtime_error(buf);
+  }
+}
+}  // namespace gwa
+
 struct gwa_index {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -196,6 +208,7 @@ struct gwa_index {
   uint64_t *d_text2 = nullptr, *d_textN = nullptr;
   uint64_t *d_kmer[2] = {nullptr, nullptr};
   int64_t *d_contig = nullptr;
+  int64_t *d_ctgLen = nullptr;   // contig lengths (the SAM writer's MD:Z windows)
   int32_t *d_chrRank = nullptr;  // String.compareTo rank of each contig name (also its SAM name key)
   char *d_ctg = nullptr;         // contig names (SAM RNAME / RNEXT text)
   uint64_t *d_ctgOff = nullptr;
@@ -344,6 +357,7 @@ static void freeIndexDev(gwa_index *ix) {
     if (ix->d_kmer[f]) (void)hipFree(ix->d_kmer[f]);
   if (ix->d_textN) (void)hipFree(ix->d_textN);
   if (ix->d_contig) (void)hipFree(ix->d_contig);
+  if (ix->d_ctgLen) (void)hipFree(ix->d_ctgLen);
   if (ix->d_chrRank) (void)hipFree(ix->d_chrRank);
   if (ix->d_ctg) (void)hipFree(ix->d_ctg);
   if (ix->d_ctgOff) (void)hipFree(ix->d_ctgOff);
@@ -412,6 +426,7 @@ static void buildFromDeviceText(gwa_index *ix, uint8_t *dT) {
   (void)hipFree(dR);
   rankNames(h);
   ix->d_contig = devUpload(h.offsets, s, &ix->bytes);
+  ix->d_ctgLen = devUpload(h.lengths, s, &ix->bytes);
   ix->d_chrRank = devUpload(h.chrRank, s, &ix->bytes);
   {  // contig names for the SAM writer
     const SamNames sn = samNames(h);
@@ -488,6 +503,7 @@ void gwa_config_default(gwa_config_t *c) {
   c->num_gap_open = 1; c->num_gap_ext = 4; c->num_split = 1;
   c->match = 1; c->mismatch = 3; c->gap_open = 11; c->gap_ext = 4; c->split_open = 11;
   c->indel_end_skip = 5; c->band_width = 31;
+  c->sam_tags = 0;
 }
 
 const char *gwa_last_error(void) { return g_err.c_str(); }
@@ -711,6 +727,7 @@ static void freeBatchDev(gwa_batch *b) {
 // Batch set-up shared by every way reads arrive: config, stream; true for -m bd / -m bwa
 static bool batchHead(gwa_index *ix, const gwa_config_t *cfg, uint32_t n, gwa_batch *b) {
   if (cfg->strategy < 0 || cfg->strategy > 3) throw std::runtime_error("unknown strategy (-m bsf, sf, bd, bwa)");
+  gwa::checkSamTags(cfg->sam_tags);
   HIPCHK(hipSetDevice(ix->device));
   b->ix = ix;
   b->cfg = *cfg;
@@ -1670,6 +1687,11 @@ static SamText samText(const gwa_batch *b) {
   t.chrKey = b->ix->d_chrRank;
   t.starKey = b->ix->starKey;
   t.emptyKey = b->ix->emptyKey;
+  t.text2 = b->ix->d_text2;
+  t.textN = b->ix->d_textN;
+  t.ctgStart = b->ix->d_contig;
+  t.ctgLen = b->ix->d_ctgLen;
+  t.tags = b->cfg.sam_tags;
   return t;
 }
 
@@ -2038,6 +2060,7 @@ int gwa_results_records(const gwa_index_t *ix, gwa_results_t *r) {
           if (f[k].second >= 5 && !memcmp(p, "NM:i:", 5)) g.nm = (int32_t)strtol(std::string(p + 5, f[k].second - 5).c_str(), nullptr, 10);
           else if (f[k].second >= 5 && !memcmp(p, "X0:i:", 5)) g.x0 = (int32_t)strtol(std::string(p + 5, f[k].second - 5).c_str(), nullptr, 10);
           else if (f[k].second >= 5 && !memcmp(p, "XP:Z:", 5)) { g.state_off = f[k].first + 5; g.state_len = (uint32_t)(f[k].second - 5); }
+          else if (f[k].second >= 5 && !memcmp(p, "MD:Z:", 5)) { g.md_off = f[k].first + 5; g.md_len = (uint32_t)(f[k].second - 5); }
         }
         // single-end results: a first line with FLAG 0x1 and without 0x80 is followed by its split
         // record (AlignmentRecord.toSAMLine, R/AlignmentRecord.java:109-170); paired-end results have

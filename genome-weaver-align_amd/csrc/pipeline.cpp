@@ -47,6 +47,7 @@
 extern "C" int gwa_fail_message(const char *msg);  // gwa_api.cpp
 
 namespace gwa {
+void checkSamTags(uint32_t tags);
 int batchCreateFastq(gwa_index_t *ix, const gwa_config_t *cfg, const char *text, uint64_t len, const uint64_t *start,
                      uint32_t n, gwa_batch_t **out);
 // a paired batch from the mates' FASTQ text: two segments, or (text2 == nullptr) one interleaved
@@ -676,6 +677,7 @@ int gwa_pipeline_open(gwa_index_t *const *ix, int n_ix, const gwa_config_t *cfg,
   try {
     if (n_ix < 1) throw std::runtime_error("gwa_pipeline_open: no index handle");
     if (cfg->strategy < 0 || cfg->strategy > 3) throw std::runtime_error("unknown strategy");
+    gwa::checkSamTags(cfg->sam_tags);
     auto *p = new gwa_pipeline();
     p->ix.assign(ix, ix + n_ix);
     p->cfg = *cfg;

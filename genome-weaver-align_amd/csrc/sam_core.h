@@ -32,7 +32,13 @@ struct SamText {
   const uint64_t *ctgOff;    // nContig + 1
   const int32_t *chrKey;     // per contig: equal names <=> equal keys (String.equals)
   int32_t starKey, emptyKey; // the keys of the names "*" and "" (a contig may be called that)
+  // optional tags (tags & kSamTagMd: MD:Z, samfmt::mdTag): the index's forward text (IndexView::text2 /
+  // textN) and each contig's start offset in it and length.  The defaults mean "no MD".
+  const uint64_t *text2 = nullptr, *textN = nullptr;
+  const int64_t *ctgStart = nullptr, *ctgLen = nullptr;
+  uint32_t tags = 0;
 };
+constexpr uint32_t kSamTagMd = 1u;  // GWA_SAM_TAG_MD (include/gwa.h)
 
 // A bulk field left to the workgroup (device write pass): out[i] = f(src[i]), or, for the reversed
 // kinds, out[i] = f(src[len - 1 - i]), at byte `at` of the workgroup's staging buffer.
@@ -241,6 +247,218 @@ GWA_HD void emitCigar(SamOut &o, const CigSpec &c) {
   e.flush();
 }
 
+// ---- MD:Z (SamText::tags & kSamTagMd) ----
+// The tag is defined from the printed line alone: walk the printed CIGAR from POS on
+// the printed contig and compare the printed SEQ with the contig; a base outside [1, contig length],
+// an N on either side and a SEQ position past the end of SEQ never match.  The reference has no MD.
+// Matches are counted 32 bases per step: the contig window as text2 / textN words, the read's codes
+// from 16-B chunks of its row packed to 2-bit fields, compared by XOR; only mismatches and deleted
+// bases are looked at one by one.
+
+// reverse the order of the 32 two-bit fields / of the 32 bits
+GWA_HD uint64_t mdRev2(uint64_t x) {
+  x = ((x >> 2) & 0x3333333333333333ULL) | ((x & 0x3333333333333333ULL) << 2);
+  x = ((x >> 4) & 0x0F0F0F0F0F0F0F0FULL) | ((x & 0x0F0F0F0F0F0F0F0FULL) << 4);
+  return __builtin_bswap64(x);
+}
+GWA_HD uint32_t mdRev1(uint32_t x) {
+  x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
+  x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
+  x = ((x >> 4) & 0x0F0F0F0Fu) | ((x & 0x0F0F0F0Fu) << 4);
+  return __builtin_bswap32(x);
+}
+
+// chunk k (16 codes 0..4) of a read's code row as 16 two-bit fields and 16 N flags; rows are 16-B
+// aligned and zero-padded to a multiple of 16 (ReadsView), chunks outside [0, m) read as zero
+GWA_HD void mdChunk(const uint8_t *row, int m, int k, uint64_t *c2, uint64_t *nn) {
+  *c2 = 0;
+  *nn = 0;
+  if (k < 0 || 16 * k >= m) return;
+  uint32_t w[4];
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint4 v = *reinterpret_cast<const uint4 *>(row + 16 * k);
+  w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+#else
+  __builtin_memcpy(w, row + 16 * k, 16);
+#endif
+  uint32_t c = 0, n = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    uint32_t x = w[i] & 0x03030303u;  // the low two bits of each byte, gathered into one byte
+    x = (x | x >> 6) & 0x000F000Fu;
+    x = (x | x >> 12) & 0xFFu;
+    uint32_t y = (w[i] >> 2) & 0x01010101u;  // bit 2 (code 4 = N) of each byte, into four bits
+    y = (y | y >> 7) & 0x00030003u;
+    y = (y | y >> 14) & 0xFu;
+    c |= x << (8 * i);
+    n |= y << (4 * i);
+  }
+  *c2 = c;
+  *nn = n;
+}
+
+// the printed SEQ: positions [seqA, seqA + seqLen) of the read row[0, m), or of its reverse complement
+struct MdSeq {
+  const uint8_t *row;
+  int m, seqA, seqLen;
+  bool rc;
+};
+
+// SEQ[q, q + 32) as two-bit fields and N flags; positions past the end of SEQ are N
+GWA_HD void mdSeqWin(const MdSeq &s, int q, uint64_t *codes, uint32_t *nb) {
+  const int left = s.seqLen - q;
+  if (left <= 0) {
+    *codes = 0;
+    *nb = 0xFFFFFFFFu;
+    return;
+  }
+  // the 32 read positions [a, a + 32) behind them (-31 <= a: the reverse strand reads them backwards)
+  const int j = s.seqA + q;
+  const int a = s.rc ? s.m - 1 - j - 31 : j;
+  const int k0 = ((a + 32) >> 4) - 2, sh = a - 16 * k0;
+  uint64_t c0, c1, c2, n0, n1, n2;
+  mdChunk(s.row, s.m, k0, &c0, &n0);
+  mdChunk(s.row, s.m, k0 + 1, &c1, &n1);
+  c2 = n2 = 0;
+  if (sh) mdChunk(s.row, s.m, k0 + 2, &c2, &n2);
+  const uint64_t lo = c0 | c1 << 32;
+  uint64_t c = sh ? (lo >> (2 * sh)) | (c2 << (64 - 2 * sh)) : lo;
+  uint32_t n = (uint32_t)((n0 | n1 << 16 | n2 << 32) >> sh);
+  if (s.rc) {
+    c = ~mdRev2(c);
+    n = mdRev1(n);
+  }
+  *codes = c;
+  *nb = left < 32 ? n | 0xFFFFFFFFu << left : n;
+}
+
+// text positions [p, p + cnt) (1 <= cnt <= 32, all inside the text) as two-bit fields and N flags
+GWA_HD void mdTextWin(const uint64_t *t2, const uint64_t *tn, int64_t p, int cnt, uint64_t *codes, uint32_t *nb) {
+  const int64_t a = p >> 5, b = p >> 6;
+  const int sa = (int)(p & 31), sn = (int)(p & 63);
+  const uint64_t a0 = t2[a], a1 = sa + cnt > 32 ? t2[a + 1] : 0ULL;
+  const uint64_t n0 = tn[b], n1 = sn + cnt > 64 ? tn[b + 1] : 0ULL;
+  *codes = sa ? (a0 >> (2 * sa)) | (a1 << (64 - 2 * sa)) : a0;
+  *nb = (uint32_t)(sn ? (n0 >> sn) | (n1 << (64 - sn)) : n0);
+}
+
+struct MdWalk {
+  SamOut o;
+  const uint64_t *t2, *tn;
+  int64_t cs, cl;  // the contig: start offset in the text, length
+  MdSeq s;
+  int64_t r;       // 1-based position on the contig (may lie outside it)
+  int q = 0;       // position in SEQ
+  int64_t run = 0;
+  int pt = -1;     // the pending CIGAR element, merged as CigEmit merges
+  int64_t pl = 0;
+
+  GWA_HD char refLetter(int64_t x) const {
+    if (x < 1 || x > cl) return 'N';
+    const int64_t p = cs + x - 1;
+    if ((tn[p >> 6] >> (p & 63)) & 1) return 'N';
+    return sym((unsigned)((t2[p >> 5] >> ((p & 31) * 2)) & 3));
+  }
+  GWA_HD void miss(char c) {
+    o.num(run);
+    o.ch(c);
+    run = 0;
+  }
+  // k bases off the contig: N, never a match
+  GWA_HD void outside(int64_t k) {
+    for (int64_t i = 0; i < k; ++i) miss('N');
+    r += k;
+    q += (int)k;
+  }
+  GWA_HD void match(int64_t l) {
+    // the element clamped to the contig, once: [r, r + l) = before | inside | behind
+    const int64_t before = r >= 1 ? 0 : (1 - r < l ? 1 - r : l);
+    const int64_t room = cl - (r + before) + 1;  // of the contig, from the first base not before it
+    int64_t inside = l - before;
+    if (inside > room) inside = room > 0 ? room : 0;
+    const int64_t behind = l - before - inside;
+    outside(before);
+    while (inside > 0) {
+      const int cnt = inside > 32 ? 32 : (int)inside;
+      uint64_t tw, sw;
+      uint32_t tN, sN;
+      mdTextWin(t2, tn, cs + r - 1, cnt, &tw, &tN);
+      mdSeqWin(s, q, &sw, &sN);
+      const uint64_t x = tw ^ sw;
+      uint64_t nz = (x | (x >> 1)) & 0x5555555555555555ULL;
+      uint32_t nm = tN | sN;
+      int base = 0;
+      for (;;) {
+        const int j1 = nz ? __builtin_ctzll(nz) >> 1 : 32, j2 = nm ? __builtin_ctz(nm) : 32;
+        const int j = j1 < j2 ? j1 : j2;
+        if (j >= cnt) break;
+        run += j - base;
+        miss(((tN >> j) & 1) ? 'N' : sym((unsigned)((tw >> (2 * j)) & 3)));
+        base = j + 1;
+        nz &= ~(3ULL << (2 * j));
+        nm &= ~(1u << j);
+      }
+      run += cnt - base;
+      r += cnt;
+      q += cnt;
+      inside -= cnt;
+    }
+    outside(behind);
+  }
+  GWA_HD void element(int t, int64_t l) {
+    if (t == 0 || t == 7) {  // M X (the writer never prints '=')
+      match(l);
+    } else if (t == 2) {  // D
+      o.num(run);
+      o.ch('^');
+      for (int64_t i = 0; i < l; ++i) o.ch(refLetter(r + i));
+      run = 0;
+      r += l;
+    } else if (t == 3) {  // N
+      r += l;
+    } else if (t == 1 || t == 4) {  // I S
+      q += (int)l;
+    }
+  }
+  GWA_HD void flush() {
+    if (pt >= 0) element(pt, pl);
+  }
+  GWA_HD void raw(int t, int64_t l) {
+    flush();
+    pt = t;
+    pl = l;
+  }
+  GWA_HD void add(int t, int64_t l) {
+    if (pt == t) pl += l;
+    else raw(t, l);
+  }
+};
+
+// "\tMD:Z:<value>" of one line at p + n (p == nullptr: counted); returns the new n.  Not inlined: the
+// writer's callers are inlined into each of samChain's record forms.
+GWA_HDNI inline uint64_t mdEmit(char *p, uint64_t n, const uint64_t *t2, const uint64_t *tn, int64_t cs, int64_t cl,
+                                int64_t pos, const uint16_t *ca, int na, int preS, int postS, const uint16_t *cb, int nb,
+                                const uint8_t *row, int m, int seqA, int seqLen, bool rc) {
+  MdWalk w{SamOut{p, n}, t2, tn, cs, cl, MdSeq{row, m, seqA, seqLen, rc}, pos};
+  w.o.lit("\tMD:Z:");
+  // the printed CIGAR's elements (emitCigar)
+  if (preS >= 0) w.add(4, preS);
+  for (int i = 0; i < na; ++i) w.raw(ca[i] & 7, ca[i] >> 3);
+  if (postS >= 0) w.add(4, postS);
+  for (int i = 0; i < nb; ++i) w.add(cb[i] & 7, cb[i] >> 3);
+  w.flush();
+  w.o.num(w.run);
+  return w.o.n;
+}
+
+// the MD tag of a mapped line on contig chr >= 0 at POS pos with the printed CIGAR c, whose SEQ is
+// [seqA, seqB) of read r's strand-oriented query
+GWA_HD void mdTag(SamOut &o, const SamText &t, uint32_t r, int chr, int64_t pos, const CigSpec &c, int seqA, int seqB,
+                  bool rc) {
+  o.n = mdEmit(o.p, o.n, t.text2, t.textN, t.ctgStart[chr], t.ctgLen[chr], pos, c.a, c.na, c.preS, c.postS, c.b, c.nb,
+               t.codes + t.codeOff[r], (int)t.codeLen[r], seqA, seqB > seqA ? seqB - seqA : 0, rc);
+}
+
 // one AlignmentRecord to print
 struct Rec {
   int chr, strand, start, end, nm, numBestHits;
@@ -347,6 +565,7 @@ GWA_HD bool lineOne(SamOut &o, Ctx &cx, const Rec &r, const Rec *split, bool has
     emitState(o, cx, r.stateHead, r.stateSelf);
     o.lit("\tX0:i:");
     o.num(r.numBestHits);
+    if ((cx.t.tags & kSamTagMd) && r.chr >= 0) mdTag(o, cx.t, cx.r, r.chr, r.start, r.cig, r.seqA, r.seqB, cx.strand != 0);
   }
   return eachMapped;
 }
@@ -547,6 +766,8 @@ GWA_HD void samMateLine(SamOut &o, const SamText &t, uint32_t r, const OutHit *h
     o.ch(h->numHits == 1 ? 'U' : 'R');
     o.lit("\tX0:i:");
     o.num(h->numHits);
+    if (t.tags & kSamTagMd)
+      samfmt::mdTag(o, t, r, h->chr, h->pos, samfmt::CigSpec{hc + h->cigarOff, (int)h->cigarLen, -1, -1, nullptr, 0}, 0, m, rev);
   }
   o.ch('\n');
 }

@@ -26,7 +26,7 @@ class GwaError(RuntimeError):
 class _Config(ctypes.Structure):
     _fields_ = [("k", ctypes.c_float)] + [(n, ctypes.c_int32) for n in (
         "strategy", "report_type", "top_l", "num_gap_open", "num_gap_ext", "num_split", "match", "mismatch",
-        "gap_open", "gap_ext", "split_open", "indel_end_skip", "band_width")]
+        "gap_open", "gap_ext", "split_open", "indel_end_skip", "band_width")] + [("sam_tags", ctypes.c_uint32)]
 
 
 class _Reads(ctypes.Structure):
@@ -44,7 +44,8 @@ class Record(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ("read", "flag")] + [(n, ctypes.c_int32) for n in (
         "ref", "pos", "end", "strand", "nm", "x0", "split", "is_split", "qual_null", "pad_")] + [
         (n, ctypes.c_uint64) for n in ("line_off", "name_off", "cigar_off", "seq_off", "qual_off", "state_off")] + [
-        (n, ctypes.c_uint32) for n in ("line_len", "name_len", "cigar_len", "seq_len", "qual_len", "state_len")]
+        (n, ctypes.c_uint32) for n in ("line_len", "name_len", "cigar_len", "seq_len", "qual_len", "state_len")] + [
+        ("md_off", ctypes.c_uint64), ("md_len", ctypes.c_uint32), ("pad2_", ctypes.c_uint32)]
 
 
 class _Results(ctypes.Structure):
@@ -169,6 +170,7 @@ def _check(rc):
 
 STRATEGIES = {"bsf": 0, "sf": 1, "bd": 2, "bwa": 3}
 REPORT_TYPES = {"besthit": 0, "allhits": 1, "topl": 2}
+SAM_TAG_MD = 1  # GWA_SAM_TAG_MD
 
 
 @dataclass
@@ -188,6 +190,7 @@ class AlignmentConfig:
     splitOpenPenalty: int = 11  # -S
     indelEndSkip: int = 5      # -P
     bandWidth: int = 31        # -W
+    mdTag: bool = False        # --md: MD:Z on every mapped line (GWA_SAM_TAG_MD; the reference prints none)
 
     def getMaximumEditDistance(self, readLength):
         # A/AlignmentScoreConfig.java:40-47 (float arithmetic)
@@ -208,6 +211,7 @@ class AlignmentConfig:
         c.match, c.mismatch, c.gap_open = self.matchScore, self.mismatchPenalty, self.gapOpenPenalty
         c.gap_ext, c.split_open = self.gapExtensionPenalty, self.splitOpenPenalty
         c.indel_end_skip, c.band_width = self.indelEndSkip, self.bandWidth
+        c.sam_tags = SAM_TAG_MD if self.mdTag else 0
         return c
 
 

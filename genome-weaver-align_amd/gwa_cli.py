@@ -125,6 +125,8 @@ def build_parser():
     a.add_argument("-S", dest="splitOpenPenalty", type=int, default=11)
     a.add_argument("-P", dest="indelEndSkip", type=int, default=5)
     a.add_argument("-W", dest="bandWidth", type=int, default=31)
+    a.add_argument("--md", dest="mdTag", action="store_true",
+                   help="append MD:Z to every mapped line (computed on the device; not in the reference's output)")
     a.add_argument("--device", type=int, default=0, help="GPU ordinal (one device)")
     a.add_argument("--devices", default=None, help="comma-separated GPU ordinals: one index replica per GPU")
     a.add_argument("--workers", type=int, default=3, help="host worker threads per device")
@@ -187,7 +189,7 @@ def config_of(ns):
                               numSplitAlowed=ns.numSplitAlowed, matchScore=ns.matchScore,
                               mismatchPenalty=ns.mismatchPenalty, gapOpenPenalty=ns.gapOpenPenalty,
                               gapExtensionPenalty=ns.gapExtensionPenalty, splitOpenPenalty=ns.splitOpenPenalty,
-                              indelEndSkip=ns.indelEndSkip, bandWidth=ns.bandWidth)
+                              indelEndSkip=ns.indelEndSkip, bandWidth=ns.bandWidth, mdTag=ns.mdTag)
     cfg._c()  # validates strategy / report type (raises GwaError)
     return cfg
 

@@ -27,7 +27,8 @@ typedef struct gwa_index gwa_index_t;
 typedef struct gwa_batch gwa_batch_t;
 
 /* AlignmentConfig + AlignmentScoreConfig (A/AlignmentConfig.java:40-72, A/AlignmentScoreConfig.java:37-77);
- * defaults from gwa_config_default: k 0.1, bsf, besthit, L 5, g 1, e 4, s 1, M 1, N 3, G 11, E 4, S 11, P 5, W 31 */
+ * defaults from gwa_config_default: k 0.1, bsf, besthit, L 5, g 1, e 4, s 1, M 1, N 3, G 11, E 4, S 11, P 5, W 31,
+ * sam_tags 0 */
 typedef struct {
   float k;
   int32_t strategy;    /* 0 = bsf (-m bsf), 1 = sf (-m sf, S/SuffixFilter.java); others are rejected */
@@ -36,7 +37,24 @@ typedef struct {
   int32_t num_gap_open, num_gap_ext, num_split; /* -g -e -s */
   int32_t match, mismatch, gap_open, gap_ext, split_open; /* -M -N -G -E -S */
   int32_t indel_end_skip, band_width; /* -P -W */
+  uint32_t sam_tags;   /* optional SAM tags, GWA_SAM_TAG_* bits; 0 = the reference's lines.  A bit that is not
+                        * defined fails gwa_batch_create*, gwa_align_* and gwa_pipeline_open
+                        * ("gwa_config_t.sam_tags: unknown bits 0x..") */
 } gwa_config_t;
+/* MD:Z on every mapped line (FLAG without 0x4, RNAME a contig), appended last, after X0:i: "\tMD:Z:<value>".
+ * Every path that formats SAM carries it: single and paired batches, results / results_range /
+ * results_select, gwa_batch_format + gwa_batch_sam_copy and the gwa_pipeline_* calls.  Removing
+ * "\tMD:Z:[^\t\n]*" from every line gives the default output byte for byte.
+ * The reference prints no MD, and some of its lines are not SAM-spec alignments (POS <= 0, an S inside
+ * the CIGAR, an alignment running past its contig's end), so the value is defined from the printed line
+ * alone: walk the printed CIGAR from q = 0 in the printed SEQ and r = POS on the printed contig; M / X
+ * compare SEQ[q] with the contig's base at r (a match iff both are one of A C G T and equal; a mismatch
+ * prints the run of matches, then the contig's letter), D prints the run, '^' and the contig's letters,
+ * N advances r, I and S advance q.  A position outside [1, contig length] reads as N (never a
+ * neighbouring contig's base), as does SEQ past its end.  The value matches
+ * [0-9]+(([ACGTN]|\^[ACGTN]+)[0-9]+)*; an empty CIGAR gives "0".  NM:i stays the reference's
+ * numMismatches, which counts a read's N as A: NM and MD may disagree where the read has an N. */
+#define GWA_SAM_TAG_MD 1u
 
 /* A batch of reads, SoA, caller-owned.  Read i = name[name_off[i], name_off[i+1]), etc.
  * qual may be NULL: no read has a quality (SAM QUAL "*", as for FASTA input / -q queries).
@@ -77,6 +95,9 @@ typedef struct {
   int32_t pad_;
   uint64_t line_off, name_off, cigar_off, seq_off, qual_off, state_off;
   uint32_t line_len, name_len, cigar_len, seq_len, qual_len, state_len;
+  uint64_t md_off;        /* the MD:Z value (GWA_SAM_TAG_MD); 0 / 0 when the line has none */
+  uint32_t md_len;
+  uint32_t pad2_;
 } gwa_record_t;
 
 /* Library-owned SAM text (no header), in input order; read i's lines are
