@@ -18,6 +18,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "bgzf_host.h"
 #include "bsf_core.h"
 #include "sf_core.h"
 #include "host_index.h"
@@ -309,6 +310,12 @@ struct gwa_batch {
   size_t fmtCap = 0, fmtTmpBytes = 0, fmtTextCap = 0;
   uint64_t fmtBytes = 0;  // the text of the last formatting, and whether it was the whole batch
   bool fmtWhole = false;
+  // BGZF of that text (bgzf.hip): per-block slots, sizes, offsets, stored count, the compacted blocks
+  uint8_t *d_bgzSlots = nullptr, *d_bgzOut = nullptr;
+  uint32_t *d_bgzSizes = nullptr, *d_bgzStored = nullptr;
+  uint64_t *d_bgzOffs = nullptr;
+  size_t bgzSlotCap = 0, bgzOutCap = 0, bgzBlockCap = 0;
+  uint64_t bgzBytes = 0;
   unsigned long long *d_stats = nullptr;
   bool statsDone = false;
   // device encoding of the read text (gwa_batch_run writes the code rows from the text every run: the
@@ -708,7 +715,8 @@ static void freeBatchDev(gwa_batch *b) {
   void *ps[] = {b->d_codes, b->d_off, b->d_len, b->d_sres, b->d_oh, b->d_hits, b->d_cig, b->d_list[0], b->d_list[1], b->d_all, b->d_count,
                 b->d_stair, b->d_stairBase, b->d_stairBad, b->d_fieldOwn[0], b->d_fieldOwn[1], b->d_fieldOwn[2],
                 b->d_fmtLen, b->d_fmtOff, b->d_fmtIdx, b->d_fmtErr, b->d_fmtTmp, b->d_fmtText, b->d_stats,
-                b->d_row, b->d_seen, b->d_encTmp, b->d_qualNull, b->d_rescue, b->d_heavy};
+                b->d_row, b->d_seen, b->d_encTmp, b->d_qualNull, b->d_rescue, b->d_heavy,
+                b->d_bgzSlots, b->d_bgzOut, b->d_bgzSizes, b->d_bgzStored, b->d_bgzOffs};
   if (b->stream) (void)hipStreamSynchronize(b->stream);  // (then every buffer below is idle)
   for (void *p : ps) batchFree(p, nullptr);
   // the text blobs (one allocation may back several of them)
@@ -1812,7 +1820,73 @@ static void formatResults(gwa_batch *b, const uint32_t *hostIdx, uint32_t first,
   out->sam_len = total;
 }
 
+// The whole batch's SAM text formatted and compressed in HBM: BGZF blocks (include/gwa.h), side by side
+// in d_bgzOut; returns their size.  compress_ms covers the block kernel, the scan and the compaction.
+static uint64_t bgzfOnDevice(gwa_batch *b) {
+  b->stats.compress_ms = 0;
+  b->stats.bgzf_bytes = b->stats.bgzf_blocks = b->stats.bgzf_stored = 0;
+  b->bgzBytes = 0;
+  if (b->headerOnly) {
+    if (!b->ran) throw std::runtime_error("gwa_batch_run has not completed");
+    b->fmtBytes = 0;
+    return 0;
+  }
+  const uint64_t n = formatOnDevice(b, nullptr, 0, b->pairs ? b->pairs : b->n);
+  b->fmtWhole = true;
+  const uint64_t nb = (n + bgzf::kSlice - 1) / bgzf::kSlice;
+  if (!nb) return 0;
+  hipStream_t s = b->stream;
+  growDev(&b->d_bgzSlots, &b->bgzSlotCap, bgzfSlotBytes(nb), s);
+  if (!b->d_bgzSizes || b->bgzBlockCap < nb) {
+    batchFree(b->d_bgzSizes, s);
+    batchFree(b->d_bgzOffs, s);
+    b->d_bgzSizes = nullptr;
+    b->d_bgzOffs = nullptr;
+    b->d_bgzSizes = bAlloc<uint32_t>(nb);
+    b->d_bgzOffs = bAlloc<uint64_t>(nb + 1);
+    b->bgzBlockCap = nb;
+  }
+  if (!b->d_bgzStored) b->d_bgzStored = bAlloc<uint32_t>(1);
+  Events ev;
+  HIPCHK(hipEventRecord(ev.e[0], s));
+  launchBgzfBlocks((const uint8_t *)b->d_fmtText, n, nb, b->d_bgzSlots, b->d_bgzSizes, b->d_bgzOffs, b->d_bgzStored, s);
+  HIPCHK(hipGetLastError());
+  uint64_t total = 0;
+  uint32_t stored = 0;
+  HIPCHK(hipMemcpyAsync(&total, b->d_bgzOffs + nb, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&stored, b->d_bgzStored, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  growDev(&b->d_bgzOut, &b->bgzOutCap, (size_t)total, s);
+  launchBgzfCompact(b->d_bgzSlots, b->d_bgzSizes, b->d_bgzOffs, nb, b->d_bgzOut, s);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ev.e[1], s));
+  HIPCHK(hipEventSynchronize(ev.e[1]));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  b->stats.compress_ms = ms;
+  b->stats.bgzf_bytes = total;
+  b->stats.bgzf_blocks = nb;
+  b->stats.bgzf_stored = stored;
+  b->bgzBytes = total;
+  return total;
+}
+
 namespace gwa {
+// batchSamInto's BGZF sibling: format, compress, compact, one D2H of the blocks into the caller's buffer
+uint64_t batchBgzfInto(gwa_batch_t *b, char **buf, uint64_t *cap) {
+  const uint64_t total = bgzfOnDevice(b);
+  if (*cap < total) {
+    if (*buf) (void)hipHostFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    const uint64_t want = total + total / 8 + (1 << 20);
+    HIPCHK(hipHostMalloc((void **)buf, want, hipHostMallocDefault));
+    *cap = want;
+  }
+  if (total) HIPCHK(hipMemcpyAsync(*buf, b->d_bgzOut, total, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return total;
+}
 // Pipeline use (pipeline.cpp): the whole batch's SAM text into a caller buffer (pinned host memory,
 // grown with hipHostMalloc as needed); returns its size.  Throws on a failing read.
 uint64_t batchSamInto(gwa_batch_t *b, char **buf, uint64_t *cap) {
@@ -1864,6 +1938,92 @@ int gwa_batch_format(gwa_batch_t *b, uint64_t *sam_bytes) {
   } catch (std::exception &e) {
     return fail(e.what());
   }
+}
+
+int gwa_batch_format_bgzf(gwa_batch_t *b, uint64_t *bgzf_bytes, uint64_t *n_blocks) {
+  try {
+    HIPCHK(hipSetDevice(b->ix->device));
+    *bgzf_bytes = bgzfOnDevice(b);
+    *n_blocks = b->stats.bgzf_blocks;
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+int gwa_batch_results_bgzf(gwa_batch_t *b, uint8_t **out, uint64_t *len) {
+  try {
+    HIPCHK(hipSetDevice(b->ix->device));
+    const uint64_t total = bgzfOnDevice(b);
+    uint8_t *p = (uint8_t *)malloc(total + 1);
+    if (!p) throw std::runtime_error("out of host memory for the BGZF blocks");
+    if (total) {
+      hipError_t e = hipMemcpyAsync(p, b->d_bgzOut, total, hipMemcpyDeviceToHost, b->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+      if (e != hipSuccess) {
+        free(p);
+        HIPCHK(e);
+      }
+    }
+    *out = p;
+    *len = total;
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+int gwa_bgzf_eof(uint8_t *out28) {
+  bgzf::eofMarker(out28);
+  return 0;
+}
+
+int gwa_bgzf_compress(int device, const void *in, uint64_t n, uint8_t **out, uint64_t *out_len) {
+  void *dIn = nullptr, *dSlots = nullptr, *dOut = nullptr;
+  uint32_t *dSizes = nullptr, *dStored = nullptr;
+  uint64_t *dOffs = nullptr;
+  uint8_t *res = nullptr;
+  try {
+    if (device < 0 || n == 0) {  // the host build of the same encoder
+      std::vector<uint8_t> v;
+      bgzf::compressHost((const uint8_t *)in, n, v);
+      res = (uint8_t *)malloc(v.size() + 1);
+      if (!res) throw std::runtime_error("out of host memory for the BGZF blocks");
+      if (!v.empty()) memcpy(res, v.data(), v.size());
+      *out = res;
+      *out_len = v.size();
+      return 0;
+    }
+    HIPCHK(hipSetDevice(device));
+    const uint64_t nb = (n + bgzf::kSlice - 1) / bgzf::kSlice;
+    HIPCHK(hipMalloc(&dIn, n + 16));
+    HIPCHK(hipMalloc(&dSlots, bgzfSlotBytes(nb)));
+    HIPCHK(hipMalloc((void **)&dSizes, nb * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&dOffs, (nb + 1) * sizeof(uint64_t)));
+    HIPCHK(hipMalloc((void **)&dStored, sizeof(uint32_t)));
+    HIPCHK(hipMemcpy(dIn, in, n, hipMemcpyHostToDevice));
+    launchBgzfBlocks((const uint8_t *)dIn, n, nb, dSlots, dSizes, dOffs, dStored, nullptr);
+    HIPCHK(hipGetLastError());
+    uint64_t total = 0;
+    HIPCHK(hipMemcpy(&total, dOffs + nb, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMalloc(&dOut, total));
+    launchBgzfCompact(dSlots, dSizes, dOffs, nb, (uint8_t *)dOut, nullptr);
+    HIPCHK(hipGetLastError());
+    res = (uint8_t *)malloc(total + 1);
+    if (!res) throw std::runtime_error("out of host memory for the BGZF blocks");
+    HIPCHK(hipMemcpy(res, dOut, total, hipMemcpyDeviceToHost));
+    *out = res;
+    *out_len = total;
+    res = nullptr;
+  } catch (std::exception &e) {
+    free(res);
+    for (void *p : {dIn, dSlots, dOut, (void *)dSizes, (void *)dStored, (void *)dOffs})
+      if (p) (void)hipFree(p);
+    return fail(e.what());
+  }
+  for (void *p : {dIn, dSlots, dOut, (void *)dSizes, (void *)dStored, (void *)dOffs})
+    if (p) (void)hipFree(p);
+  return 0;
 }
 
 int gwa_batch_sam_copy(gwa_batch_t *b, void *dst, uint64_t *len) {

@@ -65,6 +65,14 @@ void launchSamFormat(const SamText &t, const OutHeader *oh, const OutHit *hits, 
                      uint32_t first, uint32_t n, uint64_t *len, uint64_t *off, void *scanTmp, size_t *scanTmpBytes,
                      uint32_t *err, char *out, int pass, hipStream_t s, const PairSpec &ps, uint64_t totalBytes = 0);
 size_t samScanTempBytes(uint32_t n);
+// BGZF (bgzf.hip): the text in[0, n) (16-byte aligned) compressed into nBlocks = ceil(n / 65280) slots of
+// bgzfSlotBytes(nBlocks) bytes in all, the blocks' sizes, their exclusive scan (offs[nBlocks] = total) and
+// the number of stored blocks; then the blocks copied side by side into out
+size_t bgzfSlotBytes(uint64_t nBlocks);
+void launchBgzfBlocks(const uint8_t *in, uint64_t n, uint64_t nBlocks, void *slots, uint32_t *sizes, uint64_t *offs,
+                      uint32_t *stored, hipStream_t s);
+void launchBgzfCompact(const void *slots, const uint32_t *sizes, const uint64_t *offs, uint64_t nBlocks, uint8_t *out,
+                       hipStream_t s);
 size_t sortSearchListTmpBytes(uint32_t n);
 void launchSortSearchList(const uint32_t *listIn, uint32_t *listOut, uint32_t *keysIn, uint32_t *keysOut, uint32_t n,
                           const ScanRes *sres, bool byKey, void *tmp, size_t tmpBytes, hipStream_t s);

@@ -59,6 +59,7 @@ int batchCreatePairsFastq(gwa_index_t *ix, const gwa_config_t *cfg, const char *
 // the lowest pair of a paired batch whose mate names differ (false: none)
 bool batchMateNamesDiffer(gwa_batch_t *b, uint32_t *pair, std::string *name1, std::string *name2);
 uint64_t batchSamInto(gwa_batch_t *b, char **buf, uint64_t *cap);  // gwa_api.cpp
+uint64_t batchBgzfInto(gwa_batch_t *b, char **buf, uint64_t *cap);  // the same as BGZF blocks
 void pinnedFree(char *p);
 char *pinnedAlloc(uint64_t bytes);
 }
@@ -260,6 +261,7 @@ struct gwa_pipeline {
   uint32_t batchReads = 1u << 20;
   int workersPerDevice = 2;
   gwa_pipeline_stats_t stats{};
+  uint32_t outFormat = GWA_OUT_SAM;  // what file runs write (gwa_pipeline_set_output)
   BufPool pool;  // pinned read-text buffers, kept across align_file calls
   uint64_t pinnedBufs = 0, pinnedBytes = 0;  // pinned so far (lazily, by align_file)
   std::mutex samMu;
@@ -294,7 +296,7 @@ struct Run {
   std::map<uint64_t, uint64_t> sizes, offs; // batch -> SAM bytes / offset
   uint64_t cursor = 0, nextOff = 0;         // first batch whose offset is not fixed yet, its offset
   uint64_t turn = 0;                        // non-seekable output: the batch that writes next
-  std::atomic<uint64_t> fileReads{0}, fileBatches{0};
+  std::atomic<uint64_t> fileReads{0}, fileBatches{0}, outBytes{0};
   // paired-end runs.  A mate-name mismatch (GWA_PAIR_CHECK_NAMES) does not fail the run at once: the
   // batches before it, which are all with their workers by then, finish first, so that the pair
   // reported is the lowest of the whole input whatever order the batches complete in.
@@ -500,7 +502,7 @@ struct Run {
         uint64_t size = 0;
         if (rc == 0) {
           try {
-            size = gwa::batchSamInto(b, &pinned, &cap);
+            size = p->outFormat == GWA_OUT_BGZF ? gwa::batchBgzfInto(b, &pinned, &cap) : gwa::batchSamInto(b, &pinned, &cap);
           } catch (...) {
             gwa_batch_free(b);
             throw;
@@ -511,6 +513,7 @@ struct Run {
         if (rc != 0) throw std::runtime_error("batch " + std::to_string(j.id) + ": " + msg);
         const auto t4 = Clock::now();
         output(j.id, pinned, size);
+        outBytes += size;
         fileReads += nr;
         ++fileBatches;
         std::lock_guard<std::mutex> g(mu);
@@ -691,6 +694,14 @@ int gwa_pipeline_open(gwa_index_t *const *ix, int n_ix, const gwa_config_t *cfg,
 }
 
 void gwa_pipeline_close(gwa_pipeline_t *p) { delete p; }
+
+int gwa_pipeline_set_output(gwa_pipeline_t *p, uint32_t format) {
+  if (format != GWA_OUT_SAM && format != GWA_OUT_BGZF)
+    return gwa_fail_message(("gwa_pipeline_set_output: unknown format " + std::to_string(format) +
+                             " (GWA_OUT_SAM = 0, GWA_OUT_BGZF = 1)").c_str());
+  p->outFormat = format;
+  return 0;
+}
 
 int gwa_pipeline_stats(const gwa_pipeline_t *p, gwa_pipeline_stats_t *st) {
   *st = p->stats;
@@ -914,6 +925,7 @@ void finishFileRun(gwa_pipeline *p, Run &run, int fd, Clock::time_point t0, doub
   st.format_s = run.formatS;
   st.write_s = run.writeS;
   st.order_wait_s = run.waitS;
+  st.out_bytes = run.outBytes;
 }
 
 }  // namespace

@@ -64,7 +64,8 @@ class BatchStats(ctypes.Structure):
                 ("num_sw", ctypes.c_uint64), ("verify_bytes", ctypes.c_uint64),
                 ("quick_text_runs", ctypes.c_uint64), ("encode_ms", ctypes.c_double), ("format_ms", ctypes.c_double),
                 ("rescue_ms", ctypes.c_double), ("heavy_pairs", ctypes.c_uint64),
-                ("rescue_window_skipped", ctypes.c_uint64)]
+                ("rescue_window_skipped", ctypes.c_uint64), ("compress_ms", ctypes.c_double),
+                ("bgzf_bytes", ctypes.c_uint64), ("bgzf_blocks", ctypes.c_uint64), ("bgzf_stored", ctypes.c_uint64)]
 
 
 def shard_range(path, shard, nshards):
@@ -87,11 +88,30 @@ def snappy_decompress(data):
         lib().gwa_free(out)
 
 
+# the 28-byte end-of-file marker of BGZF (SAM specification 4.1.2; gwa_bgzf_eof gives the same bytes)
+BGZF_EOF = bytes([0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0,
+                  0, 0, 0, 0, 0, 0, 0, 0])
+OUTPUT_FORMATS = {"sam": 0, "bgzf": 1}  # GWA_OUT_SAM, GWA_OUT_BGZF
+
+
+def bgzf_compress(data, device=None):
+    """data as BGZF blocks, one per 65 280 bytes, without the EOF marker (include/gwa.h gwa_bgzf_compress):
+    on GPU `device`, or with device=None by the host build of the same encoder; the bytes are identical."""
+    data = bytes(data)
+    out, n = ctypes.c_void_p(), ctypes.c_uint64()
+    _check(lib().gwa_bgzf_compress(-1 if device is None else device, data, len(data), ctypes.byref(out), ctypes.byref(n)))
+    try:
+        return ctypes.string_at(out, n.value)
+    finally:
+        lib().gwa_free(out)
+
+
 class PipelineStats(ctypes.Structure):
     _fields_ = [("reads", ctypes.c_uint64), ("batches", ctypes.c_uint64), ("wall_s", ctypes.c_double),
                 ("read_s", ctypes.c_double), ("device_kernel_s", ctypes.c_double * 16), ("parse_s", ctypes.c_double),
                 ("setup_s", ctypes.c_double), ("format_s", ctypes.c_double), ("write_s", ctypes.c_double),
-                ("order_wait_s", ctypes.c_double), ("frame_s", ctypes.c_double), ("pinned_bufs", ctypes.c_uint64)]
+                ("order_wait_s", ctypes.c_double), ("frame_s", ctypes.c_double), ("pinned_bufs", ctypes.c_uint64),
+                ("out_bytes", ctypes.c_uint64)]
 
 
 _lib = None
@@ -102,7 +122,8 @@ EXPORTS = ["gwa_config_default", "gwa_last_error", "gwa_device_count", "gwa_inde
            "gwa_sam_header", "gwa_index_close", "gwa_align_batch", "gwa_results_free", "gwa_free",
            "gwa_batch_create", "gwa_batch_create_pairs", "gwa_align_pairs", "gwa_batch_run", "gwa_batch_stats", "gwa_batch_results", "gwa_batch_free",
            "gwa_batch_read_counters", "gwa_batch_results_range", "gwa_results_records", "gwa_batch_results_select", "gwa_batch_format",
-           "gwa_batch_sam_copy",
+           "gwa_batch_sam_copy", "gwa_batch_format_bgzf", "gwa_batch_results_bgzf", "gwa_bgzf_compress", "gwa_bgzf_eof",
+           "gwa_pipeline_set_output",
            "gwa_pipeline_open", "gwa_pipeline_align", "gwa_pipeline_align_file", "gwa_pipeline_align_file_range",
            "gwa_pipeline_align_pair_files", "gwa_pipeline_align_pairs", "gwa_reads_shard_range", "gwa_pipeline_stats",
            "gwa_pipeline_close", "gwa_reads_parse", "gwa_reads_free", "gwa_snappy_decompress"]
@@ -144,6 +165,11 @@ def lib():
         L.gwa_batch_results_select.argtypes = [V, V, ctypes.c_uint32, P(_Results)]
         L.gwa_batch_format.argtypes = [V, P(U64)]
         L.gwa_batch_sam_copy.argtypes = [V, V, P(U64)]
+        L.gwa_batch_format_bgzf.argtypes = [V, P(U64), P(U64)]
+        L.gwa_batch_results_bgzf.argtypes = [V, P(V), P(U64)]
+        L.gwa_bgzf_compress.argtypes = [I, ctypes.c_char_p, U64, P(V), P(U64)]
+        L.gwa_bgzf_eof.argtypes = [ctypes.c_char_p]
+        L.gwa_pipeline_set_output.argtypes = [V, ctypes.c_uint32]
         L.gwa_reads_parse.argtypes = [ctypes.c_char_p, U64, I, I, P(_ReadBuf), P(U64)]
         L.gwa_reads_free.argtypes = [P(_ReadBuf)]
         L.gwa_pipeline_open.argtypes = [V, I, P(_Config), ctypes.c_uint32, I, P(V)]
@@ -472,7 +498,10 @@ class Pipeline:
     """Multi-device driver (include/gwa.h gwa_pipeline_*): read batches dealt to several index replicas
     (one per GPU), SAM in input order.  indexes: FMIndexOnGenome handles, one per device."""
 
-    def __init__(self, indexes, config, batch_reads=1 << 20, workers_per_device=0):
+    def __init__(self, indexes, config, batch_reads=1 << 20, workers_per_device=0, output="sam"):
+        """output: what align_file / align_pair_files write, "sam" text or "bgzf" blocks (set_output)"""
+        if output not in OUTPUT_FORMATS:
+            raise GwaError("output must be one of %s, got %r" % (", ".join(sorted(OUTPUT_FORMATS)), output))
         self.indexes = list(indexes)
         arr = (ctypes.c_void_p * len(self.indexes))(*[ix.h.value if hasattr(ix.h, "value") else ix.h
                                                        for ix in self.indexes])
@@ -481,6 +510,15 @@ class Pipeline:
         c = config._c()
         _check(lib().gwa_pipeline_open(ctypes.cast(arr, ctypes.c_void_p), len(self.indexes), ctypes.byref(c),
                                        batch_reads, workers_per_device, ctypes.byref(self.h)))
+        if output != "sam":
+            self.set_output(output)
+
+    def set_output(self, output):
+        """"sam": file runs write SAM text (the default); "bgzf": each batch's text as BGZF blocks compressed on
+        its GPU -- no header and no EOF marker (gwa_pipeline_set_output).  align_batch / align_pairs return text."""
+        if output not in OUTPUT_FORMATS:
+            raise GwaError("output must be one of %s, got %r" % (", ".join(sorted(OUTPUT_FORMATS)), output))
+        _check(lib().gwa_pipeline_set_output(self.h, OUTPUT_FORMATS[output]))
 
     def align_batch(self, reads):
         """reads: list of (name, seq, qual-or-None) -> SAM text (no header), input order."""
@@ -593,6 +631,22 @@ class Batch:
         n = ctypes.c_uint64()
         _check(lib().gwa_batch_format(self.h, ctypes.byref(n)))
         return n.value
+
+    def format_bgzf(self):
+        """Format the batch's SAM text and compress it to BGZF blocks in HBM only; the size of the blocks
+        (stats(): compress_ms, bgzf_bytes, bgzf_blocks, bgzf_stored)."""
+        n, nb = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().gwa_batch_format_bgzf(self.h, ctypes.byref(n), ctypes.byref(nb)))
+        return n.value
+
+    def results_bgzf(self):
+        """The batch's SAM text as BGZF blocks (bytes, no EOF marker), compressed on the device."""
+        out, n = ctypes.c_void_p(), ctypes.c_uint64()
+        _check(lib().gwa_batch_results_bgzf(self.h, ctypes.byref(out), ctypes.byref(n)))
+        try:
+            return ctypes.string_at(out, n.value)
+        finally:
+            lib().gwa_free(out)
 
     def stats(self):
         st = BatchStats()

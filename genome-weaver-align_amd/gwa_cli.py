@@ -4,7 +4,7 @@ A/AlignmentConfig.java:40-72, A/AlignmentScoreConfig.java:37-77).
   python genome-weaver-align_amd/gwa_cli.py bwt ref.fa            (writes ref.fa.gwa.idx)
   python genome-weaver-align_amd/gwa_cli.py align -r ref.fa [-q SEQ | reads.fq[.gz|.snap] | reads.fa[.gz|.snap]]
          [-k 0.1] [-m bsf|sf|bd|bwa] [-R besthit|allhits|topL] [-L 5] [-g 1] [-e 4] [-s 1] [-M 1] [-N 3]
-         [-G 11] [-E 4] [-S 11] [-P 5] [-W 31] [--silent] [--devices 0,1,..] [--batch 1048576]
+         [-G 11] [-E 4] [-S 11] [-P 5] [-W 31] [--silent] [--devices 0,1,..] [--batch 1048576] [--md] [--bgzf]
   python genome-weaver-align_amd/gwa_cli.py align -r ref.fa mates_1.fq[.gz|.snap] mates_2.fq[.gz|.snap]
          [--insert-min 210] [--insert-max 390] [--check-mate-names]       (paired-end, two SAM lines per pair)
   python genome-weaver-align_amd/gwa_cli.py align -r ref.fa --interleaved pairs.fq   (mates alternating in one file)
@@ -16,6 +16,13 @@ replica per GPU in --devices, SAM written back in input order.  Like the referen
 files its `bwt` command wrote next to the FASTA (A/FMIndexOnGenome.java:60-86, A/BWTFiles.java:40-80),
 `align -r ref.fa` loads `ref.fa.gwa.idx` when `bwt` made one, and otherwise builds the index on the GPU
 from the FASTA.
+
+--bgzf writes the same SAM as BGZF, the blocked gzip of the SAM specification (zcat, samtools and htslib
+read it): the `@SQ` header as blocks from the host build of the encoder, every batch's records compressed
+on its GPU (gwa_pipeline_set_output; the blocks, not the text, cross PCIe), and the 28-byte EOF marker
+last.  With --shard R/N shard 0 writes the header and only shard N - 1 the EOF marker, so the shard files
+concatenated in order are one valid file that decompresses to the one-process SAM.  `align(ns, out=...)`
+takes a binary stream then.  The reference has no compressed output.
 
 Two read files (or one with --interleaved) are paired-end input: mate i of the first file with mate i
 of the second, two SAM lines per pair, streamed through the same pipeline on every device of
@@ -127,6 +134,9 @@ def build_parser():
     a.add_argument("-W", dest="bandWidth", type=int, default=31)
     a.add_argument("--md", dest="mdTag", action="store_true",
                    help="append MD:Z to every mapped line (computed on the device; not in the reference's output)")
+    a.add_argument("--bgzf", action="store_true",
+                   help="write the SAM as BGZF (blocked gzip, SAM specification 4.1), compressed on the device; "
+                        "the header first, the EOF marker last")
     a.add_argument("--device", type=int, default=0, help="GPU ordinal (one device)")
     a.add_argument("--devices", default=None, help="comma-separated GPU ordinals: one index replica per GPU")
     a.add_argument("--workers", type=int, default=3, help="host worker threads per device")
@@ -249,7 +259,15 @@ def align(ns, out=sys.stdout):
     t0 = time.perf_counter()
     fms = load_indexes(ns.refSeq, devices)
     t1 = time.perf_counter()
-    w = (lambda s: None) if ns.silent else out.write
+    bgzf = getattr(ns, "bgzf", False)
+    if bgzf and out is sys.stdout:
+        out = sys.stdout.buffer
+    if ns.silent:
+        w = lambda s: None  # noqa: E731
+    elif bgzf:  # (the header, or -q's few lines: the host build of the encoder)
+        w = lambda s: out.write(gwa.bgzf_compress(s.encode()))  # noqa: E731
+    else:
+        w = out.write
     if shard is None or shard[0] == 0:
         w(fms[0].samHeader())
     n = 0
@@ -270,7 +288,8 @@ def align(ns, out=sys.stdout):
         else:
             out.flush()
             tp = time.perf_counter()
-            pipe = gwa.Pipeline(fms, cfg, batch_reads=ns.batch, workers_per_device=ns.workers)  # pins host buffers
+            pipe = gwa.Pipeline(fms, cfg, batch_reads=ns.batch, workers_per_device=ns.workers,
+                                output="bgzf" if bgzf else "sam")  # pins host buffers
             t_open = time.perf_counter() - tp
             try:
                 # --warm-passes N: N - 1 untimed passes over the file into /dev/null first (pinned buffers,
@@ -296,15 +315,15 @@ def align(ns, out=sys.stdout):
                         if ns.timing:
                             st = pipe.stats()
                             print("[gwa] pipeline %.2fs: read %.2fs, frame %.2fs; summed over %d worker threads: parse %.2fs, "
-                                  "set-up %.2fs, kernels %s s, SAM format %.2fs, write %.2fs, order wait %.2fs"
+                                  "set-up %.2fs, kernels %s s, SAM format %.2fs, write %.2fs, order wait %.2fs; %d bytes out"
                                   % (st.wall_s, st.read_s, st.frame_s, ns.workers * len(devices), st.parse_s, st.setup_s,
                                      "/".join("%.2f" % st.device_kernel_s[i] for i in range(len(devices))),
-                                     st.format_s, st.write_s, st.order_wait_s), file=sys.stderr)
+                                     st.format_s, st.write_s, st.order_wait_s, st.out_bytes), file=sys.stderr)
                     else:  # an in-memory stream (tests): through a temporary file
                         with tempfile.TemporaryFile() as tf:
                             n = run_file(pipe, tf.fileno())
                             tf.seek(0)
-                            out.write(tf.read().decode())
+                            out.write(tf.read() if bgzf else tf.read().decode())
             finally:
                 t2 = time.perf_counter()  # (the SAM is written; unpinning the buffers is teardown)
                 if ns.timing and ns.sync and mono0 is not None:  # (None: a warm pass or the sync wait failed)
@@ -312,6 +331,9 @@ def align(ns, out=sys.stdout):
                 pipe.close()
         if ns.query is not None:
             t2 = time.perf_counter()
+        if bgzf and not ns.silent and (shard is None or shard[0] == shard[1] - 1):
+            out.write(gwa.BGZF_EOF)
+            out.flush()
     finally:
         for fm in fms:
             fm.close()

@@ -142,6 +142,11 @@ typedef struct {
   uint64_t rescue_window_skipped; /* paired-end: mate rescues not tried, because the mate is longer than
                                    * 256 bp or the window the insert range allows (max_insert - min_insert
                                    * + m + 2 kr) exceeds 320 bases */
+  double compress_ms;      /* the last BGZF compression of the batch's SAM text on the device: block kernel,
+                            * size scan and compaction (gwa_batch_format_bgzf / results_bgzf; HIP events) */
+  uint64_t bgzf_bytes;     /* its output, */
+  uint64_t bgzf_blocks;    /* blocks (ceil(SAM bytes / 65280)) */
+  uint64_t bgzf_stored;    /* and how many of them are stored blocks (deflate would not have been smaller) */
 } gwa_batch_stats_t;
 
 void gwa_config_default(gwa_config_t *cfg);
@@ -211,6 +216,28 @@ int gwa_batch_format(gwa_batch_t *b, uint64_t *sam_bytes);
  * device-side gather of the SAM of several GPUs over RCCL / xGMI (genome-weaver-align_amd/dist.py
  * gather_sam_device; SURVEY.md §8e's optional collective). */
 int gwa_batch_sam_copy(gwa_batch_t *b, void *dst, uint64_t *len);
+
+/* ---- BGZF output (the blocked gzip of the SAM specification, section 4.1), compressed on the device ----
+ * The compressed form of a text T is one BGZF block per 65 280-byte slice of T (the last slice shorter;
+ * an empty T gives no block).  A block is the 18 header bytes 1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43
+ * 02 00 + BSIZE (u16 LE, block size - 1), one raw deflate stream that is a single final block with
+ * dynamic Huffman codes (match lengths 3-258, distances 1-32768, never reaching before the slice), then
+ * CRC32 and ISIZE (u32 LE each) of the slice.  Where the deflate payload would exceed the slice's length
+ * + 5 bytes the block is a stored block, so every block is at most 65 311 bytes.  The blocks in order
+ * decompress to T byte for byte (gzip -d, zcat, htslib), and the same T gives the same bytes on every
+ * run, on the device and in the host build of the encoder.  The reference has no compressed output. */
+#define GWA_OUT_SAM  0u
+#define GWA_OUT_BGZF 1u
+/* The batch's SAM text formatted and compressed in HBM only (timing counterpart of gwa_batch_format, which
+ * it includes: gwa_batch_sam_copy gives the plain text afterwards). */
+int gwa_batch_format_bgzf(gwa_batch_t *b, uint64_t *bgzf_bytes, uint64_t *n_blocks);
+/* The same bytes in library-owned host memory (gwa_free).  -m bd / -m bwa: no block. */
+int gwa_batch_results_bgzf(gwa_batch_t *b, uint8_t **out, uint64_t *len);
+/* Any bytes -> BGZF blocks (no EOF marker) in library-owned memory (gwa_free): device >= 0 runs the
+ * kernels there, device < 0 the host build of the same encoder (no GPU needed); identical bytes. */
+int gwa_bgzf_compress(int device, const void *in, uint64_t n, uint8_t **out, uint64_t *out_len);
+/* The 28-byte end-of-file marker of the specification (an empty block). */
+int gwa_bgzf_eof(uint8_t *out28);
 /* SAM for reads [first, first+count) only (n_reads = count). */
 int gwa_batch_results_range(gwa_batch_t *b, uint32_t first, uint32_t count, gwa_results_t *out);
 void gwa_batch_free(gwa_batch_t *b);
@@ -249,6 +276,7 @@ typedef struct {
   double parse_s, setup_s, format_s, write_s, order_wait_s;
   double frame_s;  /* reader thread: framing the text into batches of complete records */
   uint64_t pinned_bufs;  /* align_file: pinned read-text buffers large enough for this file's chunks */
+  uint64_t out_bytes;    /* align_file / align_pair_files: bytes written to fd (SAM text, or BGZF blocks) */
 } gwa_pipeline_stats_t;
 int gwa_pipeline_open(gwa_index_t *const *ix, int n_ix, const gwa_config_t *cfg, uint32_t batch_reads,
                       int workers_per_device, gwa_pipeline_t **out);
@@ -295,6 +323,13 @@ int gwa_reads_shard_range(const char *path, uint32_t shard, uint32_t nshards, ui
  * a snappy-java stream (magic header, then length-prefixed Snappy blocks) or one bare Snappy block,
  * decompressed into *out (malloc'd, NUL-terminated; gwa_free).  Host only, no device needed. */
 int gwa_snappy_decompress(const uint8_t *in, uint64_t n, char **out, uint64_t *out_len);
+/* What gwa_pipeline_align_file / _file_range / _pair_files write to fd from now on: GWA_OUT_SAM (the
+ * default) or GWA_OUT_BGZF -- each batch's SAM text as its own run of BGZF blocks (compressed on the
+ * batch's device, one D2H of the blocks), in input order under the same pwrite / write rules; no header
+ * and no EOF marker: the caller frames the file, as it writes the @SQ header.  gwa_pipeline_align and
+ * gwa_pipeline_align_pairs return text either way.  Another value fails ("gwa_pipeline_set_output:
+ * unknown format N"). */
+int gwa_pipeline_set_output(gwa_pipeline_t *p, uint32_t format);
 int gwa_pipeline_stats(const gwa_pipeline_t *p, gwa_pipeline_stats_t *st);
 void gwa_pipeline_close(gwa_pipeline_t *p);
 
