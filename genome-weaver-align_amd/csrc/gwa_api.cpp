@@ -18,6 +18,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "bam_core.h"
 #include "bgzf_host.h"
 #include "bsf_core.h"
 #include "sf_core.h"
@@ -1713,8 +1714,9 @@ static void growDev(T **p, size_t *cap, size_t need, hipStream_t s) {
 }
 
 // SAM text of the reads idx[0..count) (or first .. first + count - 1) written on the device
-// (batch_io.hip) into d_fmtText, line offsets in d_fmtOff; returns the text size in bytes
-static uint64_t formatOnDevice(gwa_batch *b, const uint32_t *hostIdx, uint32_t first, uint32_t count) {
+// (batch_io.hip) into d_fmtText, line offsets in d_fmtOff; returns the text size in bytes.
+// bam: their BAM records instead (bam.hip; include/gwa.h), timed as bam_ms.
+static uint64_t formatOnDevice(gwa_batch *b, const uint32_t *hostIdx, uint32_t first, uint32_t count, bool bam = false) {
   if (!b->ran) throw std::runtime_error("gwa_batch_run has not completed");
   const uint32_t n = count;
   HIPCHK(hipSetDevice(b->ix->device));
@@ -1732,27 +1734,34 @@ static uint64_t formatOnDevice(gwa_batch *b, const uint32_t *hostIdx, uint32_t f
     b->d_fmtTmp = bAlloc<uint8_t>(b->fmtTmpBytes);
     b->fmtCap = (size_t)n + 1;
   }
-  if (!b->d_fmtErr) b->d_fmtErr = bAlloc<uint32_t>(1);
+  if (!b->d_fmtErr) b->d_fmtErr = bAlloc<uint32_t>(2);  // ([1]: launchBamFormat's second word)
   const uint32_t *dIdx = nullptr;
   if (hostIdx) {
     HIPCHK(hipMemcpyAsync(b->d_fmtIdx, hostIdx, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     dIdx = b->d_fmtIdx;
   }
-  HIPCHK(hipMemsetAsync(b->d_fmtErr, 0xFF, sizeof(uint32_t), s));
+  HIPCHK(hipMemsetAsync(b->d_fmtErr, 0xFF, 2 * sizeof(uint32_t), s));
   Events ev;
   HIPCHK(hipEventRecord(ev.e[0], s));
   const SamText t = samText(b);
   const PairSpec ps{b->pairs, b->minIns, b->maxIns, b->pairs ? b->d_rescue : nullptr};
   size_t tmpBytes = b->fmtTmpBytes;
-  launchSamFormat(t, b->d_oh, b->d_hits, b->d_cig, dIdx, first, n, b->d_fmtLen, b->d_fmtOff, b->d_fmtTmp, &tmpBytes,
-                  b->d_fmtErr, nullptr, 0, s, ps);
-  launchSamFormat(t, b->d_oh, b->d_hits, b->d_cig, dIdx, first, n, b->d_fmtLen, b->d_fmtOff, b->d_fmtTmp, &tmpBytes,
-                  b->d_fmtErr, nullptr, 1, s, ps);
+  auto pass = [&](int k, char *out, uint64_t totalBytes) {
+    if (bam)
+      launchBamFormat(t, b->d_oh, b->d_hits, b->d_cig, dIdx, first, n, b->d_fmtLen, b->d_fmtOff, b->d_fmtTmp, &tmpBytes,
+                      b->d_fmtErr, (uint8_t *)out, k, s, ps, totalBytes);
+    else
+      launchSamFormat(t, b->d_oh, b->d_hits, b->d_cig, dIdx, first, n, b->d_fmtLen, b->d_fmtOff, b->d_fmtTmp, &tmpBytes,
+                      b->d_fmtErr, out, k, s, ps, totalBytes);
+  };
+  pass(0, nullptr, 0);
+  pass(1, nullptr, 0);
   uint64_t total = 0;
-  uint32_t err = 0;
+  uint32_t err = 0, errs[2] = {0, 0};
   HIPCHK(hipMemcpyAsync(&total, b->d_fmtOff + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&err, b->d_fmtErr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(errs, b->d_fmtErr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
+  err = errs[0];
   if (err != 0xFFFFFFFFu) {  // a read the reference would abort on, or whose search failed
     uint32_t r = hostIdx ? hostIdx[err] : first + err;
     if (b->pairs) {  // the failing mate of pair r
@@ -1773,14 +1782,34 @@ static uint64_t formatOnDevice(gwa_batch *b, const uint32_t *hostIdx, uint32_t f
                                          : stt == ST_ERROR ? "reference would abort (exception) at read "
                                                            : "reference would abort (exception in AlignmentRecord.convert) at read ") + nm);
   }
+  if (bam && errs[1] != 0xFFFFFFFFu) {  // a read name that does not fit a record (include/gwa.h)
+    uint32_t r = hostIdx ? hostIdx[errs[1]] : first + errs[1];
+    auto nameLen = [&](uint32_t x) {
+      uint64_t no[2];
+      HIPCHK(hipMemcpy(&no[0], b->d_nameB + x, 8, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(&no[1], b->d_nameE + x, 8, hipMemcpyDeviceToHost));
+      return no[1] - no[0];
+    };
+    uint64_t nl = nameLen(r);
+    if (nl <= kBamNameMax && b->pairs) {  // pair r: its mate 2
+      r += b->pairs;
+      nl = nameLen(r);
+    }
+    throw std::runtime_error("BAM: read " + std::to_string(r) + " has a name of " + std::to_string(nl) +
+                             " bytes (at most " + std::to_string(kBamNameMax) + " fit a record)");
+  }
   growDev(&b->d_fmtText, &b->fmtTextCap, (size_t)total + 1, s);
-  launchSamFormat(t, b->d_oh, b->d_hits, b->d_cig, dIdx, first, n, b->d_fmtLen, b->d_fmtOff, b->d_fmtTmp, &tmpBytes,
-                  b->d_fmtErr, b->d_fmtText, 2, s, ps, total);
+  pass(2, b->d_fmtText, total);
   HIPCHK(hipEventRecord(ev.e[1], s));
   HIPCHK(hipEventSynchronize(ev.e[1]));
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-  b->stats.format_ms = ms;
+  if (bam) {
+    b->stats.bam_ms = ms;
+    b->stats.bam_bytes = total;
+  } else {
+    b->stats.format_ms = ms;
+  }
   b->fmtBytes = total;
   b->fmtWhole = false;
   return total;
@@ -1820,19 +1849,25 @@ static void formatResults(gwa_batch *b, const uint32_t *hostIdx, uint32_t first,
   out->sam_len = total;
 }
 
-// The whole batch's SAM text formatted and compressed in HBM: BGZF blocks (include/gwa.h), side by side
-// in d_bgzOut; returns their size.  compress_ms covers the block kernel, the scan and the compaction.
-static uint64_t bgzfOnDevice(gwa_batch *b) {
+// The whole batch's SAM text (bam: its BAM records) formatted and compressed in HBM: BGZF blocks
+// (include/gwa.h), side by side in d_bgzOut; returns their size.  compress_ms covers the block kernel, the
+// scan and the compaction.
+static uint64_t bgzfOnDevice(gwa_batch *b, bool bam = false) {
   b->stats.compress_ms = 0;
   b->stats.bgzf_bytes = b->stats.bgzf_blocks = b->stats.bgzf_stored = 0;
   b->bgzBytes = 0;
   if (b->headerOnly) {
     if (!b->ran) throw std::runtime_error("gwa_batch_run has not completed");
     b->fmtBytes = 0;
+    if (bam) {
+      b->fmtWhole = false;
+      b->stats.bam_ms = 0;
+      b->stats.bam_bytes = 0;
+    }
     return 0;
   }
-  const uint64_t n = formatOnDevice(b, nullptr, 0, b->pairs ? b->pairs : b->n);
-  b->fmtWhole = true;
+  const uint64_t n = formatOnDevice(b, nullptr, 0, b->pairs ? b->pairs : b->n, bam);
+  b->fmtWhole = !bam;
   const uint64_t nb = (n + bgzf::kSlice - 1) / bgzf::kSlice;
   if (!nb) return 0;
   hipStream_t s = b->stream;
@@ -1873,8 +1908,8 @@ static uint64_t bgzfOnDevice(gwa_batch *b) {
 
 namespace gwa {
 // batchSamInto's BGZF sibling: format, compress, compact, one D2H of the blocks into the caller's buffer
-uint64_t batchBgzfInto(gwa_batch_t *b, char **buf, uint64_t *cap) {
-  const uint64_t total = bgzfOnDevice(b);
+static uint64_t batchBlocksInto(gwa_batch_t *b, char **buf, uint64_t *cap, bool bam) {
+  const uint64_t total = bgzfOnDevice(b, bam);
   if (*cap < total) {
     if (*buf) (void)hipHostFree(*buf);
     *buf = nullptr;
@@ -1887,6 +1922,9 @@ uint64_t batchBgzfInto(gwa_batch_t *b, char **buf, uint64_t *cap) {
   HIPCHK(hipStreamSynchronize(b->stream));
   return total;
 }
+uint64_t batchBgzfInto(gwa_batch_t *b, char **buf, uint64_t *cap) { return batchBlocksInto(b, buf, cap, false); }
+// and the BAM one: the batch's records as BGZF blocks
+uint64_t batchBamInto(gwa_batch_t *b, char **buf, uint64_t *cap) { return batchBlocksInto(b, buf, cap, true); }
 // Pipeline use (pipeline.cpp): the whole batch's SAM text into a caller buffer (pinned host memory,
 // grown with hipHostMalloc as needed); returns its size.  Throws on a failing read.
 uint64_t batchSamInto(gwa_batch_t *b, char **buf, uint64_t *cap) {
@@ -1967,6 +2005,80 @@ int gwa_batch_results_bgzf(gwa_batch_t *b, uint8_t **out, uint64_t *len) {
     }
     *out = p;
     *len = total;
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+// device bytes [0, total) of the batch's stream into library-owned host memory
+static void copyOut(gwa_batch_t *b, const void *dev, uint64_t total, const char *what, uint8_t **out, uint64_t *len) {
+  uint8_t *p = (uint8_t *)malloc(total + 1);
+  if (!p) throw std::runtime_error(std::string("out of host memory for ") + what);
+  if (total) {
+    hipError_t e = hipMemcpyAsync(p, dev, total, hipMemcpyDeviceToHost, b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e != hipSuccess) {
+      free(p);
+      HIPCHK(e);
+    }
+  }
+  *out = p;
+  *len = total;
+}
+
+// the whole batch's BAM records in d_fmtText; returns their size
+static uint64_t bamOnDevice(gwa_batch_t *b) {
+  HIPCHK(hipSetDevice(b->ix->device));
+  b->fmtWhole = false;
+  if (b->headerOnly) {
+    if (!b->ran) throw std::runtime_error("gwa_batch_run has not completed");
+    b->fmtBytes = 0;
+    b->stats.bam_ms = 0;
+    b->stats.bam_bytes = 0;
+    return 0;
+  }
+  return formatOnDevice(b, nullptr, 0, b->pairs ? b->pairs : b->n, true);
+}
+
+int gwa_batch_format_bam(gwa_batch_t *b, uint64_t *bam_bytes) {
+  try {
+    *bam_bytes = bamOnDevice(b);
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+int gwa_batch_results_bam_records(gwa_batch_t *b, uint8_t **out, uint64_t *len) {
+  try {
+    const uint64_t total = bamOnDevice(b);
+    copyOut(b, b->d_fmtText, total, "the BAM records", out, len);
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+int gwa_batch_results_bam(gwa_batch_t *b, uint8_t **out, uint64_t *len) {
+  try {
+    HIPCHK(hipSetDevice(b->ix->device));
+    const uint64_t total = bgzfOnDevice(b, true);
+    copyOut(b, b->d_bgzOut, total, "the BGZF blocks", out, len);
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+int gwa_bam_header(const gwa_index_t *ix, uint8_t **out, uint64_t *len) {
+  try {
+    const std::string h = bamHeader(ix->host);
+    uint8_t *p = (uint8_t *)malloc(h.size() + 1);
+    if (!p) throw std::runtime_error("out of host memory for the BAM header");
+    memcpy(p, h.data(), h.size());
+    *out = p;
+    *len = h.size();
     return 0;
   } catch (std::exception &e) {
     return fail(e.what());

@@ -65,6 +65,11 @@ void launchSamFormat(const SamText &t, const OutHeader *oh, const OutHit *hits, 
                      uint32_t first, uint32_t n, uint64_t *len, uint64_t *off, void *scanTmp, size_t *scanTmpBytes,
                      uint32_t *err, char *out, int pass, hipStream_t s, const PairSpec &ps, uint64_t totalBytes = 0);
 size_t samScanTempBytes(uint32_t n);
+// bam.hip: the same three passes for BAM alignment records (include/gwa.h); err points at two words, the
+// lowest unit the SAM writer fails on too and the lowest unit whose read name is longer than 254 bytes
+void launchBamFormat(const SamText &t, const OutHeader *oh, const OutHit *hits, const uint16_t *cig, const uint32_t *idx,
+                     uint32_t first, uint32_t n, uint64_t *len, uint64_t *off, void *scanTmp, size_t *scanTmpBytes,
+                     uint32_t *err, uint8_t *out, int pass, hipStream_t s, const PairSpec &ps, uint64_t totalBytes = 0);
 // BGZF (bgzf.hip): the text in[0, n) (16-byte aligned) compressed into nBlocks = ceil(n / 65280) slots of
 // bgzfSlotBytes(nBlocks) bytes in all, the blocks' sizes, their exclusive scan (offs[nBlocks] = total) and
 // the number of stored blocks; then the blocks copied side by side into out

@@ -60,6 +60,7 @@ int batchCreatePairsFastq(gwa_index_t *ix, const gwa_config_t *cfg, const char *
 bool batchMateNamesDiffer(gwa_batch_t *b, uint32_t *pair, std::string *name1, std::string *name2);
 uint64_t batchSamInto(gwa_batch_t *b, char **buf, uint64_t *cap);  // gwa_api.cpp
 uint64_t batchBgzfInto(gwa_batch_t *b, char **buf, uint64_t *cap);  // the same as BGZF blocks
+uint64_t batchBamInto(gwa_batch_t *b, char **buf, uint64_t *cap);   // the batch's BAM records as BGZF blocks
 void pinnedFree(char *p);
 char *pinnedAlloc(uint64_t bytes);
 }
@@ -502,7 +503,9 @@ struct Run {
         uint64_t size = 0;
         if (rc == 0) {
           try {
-            size = p->outFormat == GWA_OUT_BGZF ? gwa::batchBgzfInto(b, &pinned, &cap) : gwa::batchSamInto(b, &pinned, &cap);
+            size = p->outFormat == GWA_OUT_BAM    ? gwa::batchBamInto(b, &pinned, &cap)
+                   : p->outFormat == GWA_OUT_BGZF ? gwa::batchBgzfInto(b, &pinned, &cap)
+                                                  : gwa::batchSamInto(b, &pinned, &cap);
           } catch (...) {
             gwa_batch_free(b);
             throw;
@@ -696,9 +699,9 @@ int gwa_pipeline_open(gwa_index_t *const *ix, int n_ix, const gwa_config_t *cfg,
 void gwa_pipeline_close(gwa_pipeline_t *p) { delete p; }
 
 int gwa_pipeline_set_output(gwa_pipeline_t *p, uint32_t format) {
-  if (format != GWA_OUT_SAM && format != GWA_OUT_BGZF)
+  if (format != GWA_OUT_SAM && format != GWA_OUT_BGZF && format != GWA_OUT_BAM)
     return gwa_fail_message(("gwa_pipeline_set_output: unknown format " + std::to_string(format) +
-                             " (GWA_OUT_SAM = 0, GWA_OUT_BGZF = 1)").c_str());
+                             " (GWA_OUT_SAM = 0, GWA_OUT_BGZF = 1, GWA_OUT_BAM = 2)").c_str());
   p->outFormat = format;
   return 0;
 }

@@ -238,6 +238,21 @@ struct CigEmit {
   }
 };
 
+// The items of c handed to e (raw / add / flush as CigEmit has them): the printed CIGAR's elements, for
+// the BAM writer (bam_core.h).  emitCigar below, lineOne and samMateLine keep their own statements next to
+// cigarItems, lineFlag, rnextSame and mateFlag: routing the SAM emitters through the helpers changes the
+// code the compiler generates for samLenKernel / samWriteKernel, and those kernels are to stay as they are
+// (their disassembly is unchanged).  tests/test_bam_host.py holds the two sides together: every BAM field is
+// compared with the line the SAM emitter prints for the same hits.
+template <class E>
+GWA_HD void cigarItems(E &e, const CigSpec &c) {
+  if (c.preS >= 0) e.add(4, c.preS);
+  for (int i = 0; i < c.na; ++i) e.raw(c.a[i] & 7, c.a[i] >> 3);
+  if (c.postS >= 0) e.add(4, c.postS);
+  for (int i = 0; i < c.nb; ++i) e.add(c.b[i] & 7, c.b[i] >> 3);
+  e.flush();
+}
+
 GWA_HD void emitCigar(SamOut &o, const CigSpec &c) {
   CigEmit e(o);
   if (c.preS >= 0) e.add(4, c.preS);
@@ -506,7 +521,8 @@ GWA_HD void emitQual(SamOut &o, const Ctx &cx, int a, int b) {
   o.qual(cx.t.qual + cx.q0, cx.qn, a, b, cx.strand != 0);
 }
 
-GWA_HD void emitState(SamOut &o, const Ctx &cx, int head, int self) {
+template <class O>
+GWA_HD void emitState(O &o, const Ctx &cx, int head, int self) {
   for (int t = head; t >= 0; t = cx.hits[t].next) {
     const char c = stateCh(cx.hits[t].numHits);
     o.ch(t == self ? c : (char)(c - 'A' + 'a'));
@@ -515,6 +531,30 @@ GWA_HD void emitState(SamOut &o, const Ctx &cx, int head, int self) {
 
 // AlignmentRecord.toSAMLine (R/AlignmentRecord.java:109-170) of one record; returns the
 // eachFragmentIsMapped value handed on to the split record's line
+// FLAG of one record's line as lineOne computes it; eachMapped is updated to the value handed on to the
+// split record's line
+GWA_HD int lineFlag(const Rec &r, const Rec *split, bool hasSegments, bool isFirst, bool &eachMapped) {
+  int flag = 0;
+  if (hasSegments) flag |= 0x1;
+  if (r.strand == 1) flag |= 0x10;
+  if (isFirst) {
+    flag |= 0x40;
+    if (r.numBestHits <= 0 || (split && split->numBestHits <= 0)) eachMapped = false;
+  } else if (!split) {
+    flag |= 0x80;
+  }
+  if (eachMapped) flag |= 0x2;
+  if (r.numBestHits <= 0) flag |= 0x4;
+  if (split && split->numBestHits <= 0) flag |= 0x8;
+  return flag;
+}
+
+// lineOne's RNEXT prints "=": both contigs are named alike and not "*"
+GWA_HD bool rnextSame(const Ctx &cx, const Rec &r, const Rec &split) {
+  const int32_t ck = nameKey(cx, r.chr), sk = nameKey(cx, split.chr);
+  return r.chr != CHR_NULL && split.chr != CHR_NULL && ck != cx.t.starKey && ck == sk;
+}
+
 GWA_HD bool lineOne(SamOut &o, Ctx &cx, const Rec &r, const Rec *split, bool hasSegments, bool isFirst, bool eachMapped) {
   int flag = 0;
   if (hasSegments) flag |= 0x1;
@@ -579,11 +619,19 @@ GWA_HD void emitRec(SamOut &o, Ctx &cx, const Rec &r, const Rec *split, bool has
   }
 }
 
+// the end of a chain's records
+GWA_HD void chainEnd(SamOut &o, const Ctx &) { o.ch('\n'); }
+
 }  // namespace samfmt
+
+// samChain, samRead and samPair choose the records (the split forms, the pair choice, the rescued mate)
+// for any sink O that has emitRec / chainEnd / samUnmapped / samMateLine overloads: SamOut here, the BAM
+// records' BamOut in bam_core.h.
 
 // One reported ReadHit chain (head = index into hits) -> SAM text, '\n' terminated.  Returns 0, or
 // -1 where the reference would throw (the run aborts, S/BidirectionalSuffixFilter.java:264-267).
-GWA_HD int samChain(SamOut &o, const SamText &t, uint32_t r, const OutHit *hits, const uint16_t *cig, int head) {
+template <class O>
+GWA_HD int samChain(O &o, const SamText &t, uint32_t r, const OutHit *hits, const uint16_t *cig, int head) {
   using namespace samfmt;
   const OutHit &h = hits[head];
   Ctx cx{t, r, hits, (int)t.codeLen[r], h.strand != 0 ? 1 : 0, qualAbsent(t, r), 0, 0};
@@ -661,7 +709,7 @@ GWA_HD int samChain(SamOut &o, const SamText &t, uint32_t r, const OutHit *hits,
       emitRec(o, cx, rec, nullptr, false);
     }
   }
-  o.ch('\n');
+  chainEnd(o, cx);
   return cx.npe ? -1 : 0;
 }
 
@@ -679,7 +727,8 @@ GWA_HD void samUnmapped(SamOut &o, const SamText &t, uint32_t r) {
 
 // Every record of read r: its reported chains (OutHeader: hits at hitOff, CIGAR ops at cigOff,
 // chains back to back) or the unmapped record.  0, or -1 where the reference would throw.
-GWA_HD int samRead(SamOut &o, const SamText &t, uint32_t r, const OutHeader &h, const OutHit *hits, const uint16_t *cig) {
+template <class O>
+GWA_HD int samRead(O &o, const SamText &t, uint32_t r, const OutHeader &h, const OutHit *hits, const uint16_t *cig) {
   if (h.status == ST_UNMAPPED) {
     samUnmapped(o, t, r);
     return 0;
@@ -713,6 +762,16 @@ GWA_HD int samRefLen(const uint16_t *cig, const OutHit &h) {
 }
 
 // one mate's SAM line; h / mate = its chosen hit and its mate's (nullptr: unmapped)
+// FLAG of a mate's line as samMateLine computes it
+GWA_HD int mateFlag(const OutHit *h, const OutHit *mate, bool first, bool proper) {
+  int flag = 0x1 | (first ? 0x40 : 0x80);
+  if (proper) flag |= 0x2;
+  if (!h) flag |= 0x4;
+  if (!mate) flag |= 0x8;
+  if (h && h->strand == 1) flag |= 0x10;
+  if (mate && mate->strand == 1) flag |= 0x20;
+  return flag;
+}
 GWA_HD void samMateLine(SamOut &o, const SamText &t, uint32_t r, const OutHit *h, const uint16_t *hc, const OutHit *mate,
                         bool first, bool proper, bool leftmost, int64_t tlenAbs, bool sameChr) {
   int flag = 0x1 | (first ? 0x40 : 0x80);
@@ -863,7 +922,8 @@ GWA_HD PairChoice pairChoose(const SamText &t, uint32_t i, uint32_t np, const Ou
 
 // Pair i: choose the mates' hits (orc_align_pairs rules 1-3; rule 3's rescued hit from `resc`, the
 // pair_rescue kernel's output) and write both lines.  -1 where a mate's search failed.
-GWA_HD int samPair(SamOut &o, const SamText &t, uint32_t i, uint32_t np, const OutHeader *oh, const OutHit *hits,
+template <class O>
+GWA_HD int samPair(O &o, const SamText &t, uint32_t i, uint32_t np, const OutHeader *oh, const OutHit *hits,
                    const uint16_t *cig, int32_t minIns, int32_t maxIns, const RescueOut *resc) {
   PairChoice P;
   if (resc) {  // the choice made by pair_rescue_kernel / pair_choose_kernel

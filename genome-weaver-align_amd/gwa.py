@@ -65,7 +65,8 @@ class BatchStats(ctypes.Structure):
                 ("quick_text_runs", ctypes.c_uint64), ("encode_ms", ctypes.c_double), ("format_ms", ctypes.c_double),
                 ("rescue_ms", ctypes.c_double), ("heavy_pairs", ctypes.c_uint64),
                 ("rescue_window_skipped", ctypes.c_uint64), ("compress_ms", ctypes.c_double),
-                ("bgzf_bytes", ctypes.c_uint64), ("bgzf_blocks", ctypes.c_uint64), ("bgzf_stored", ctypes.c_uint64)]
+                ("bgzf_bytes", ctypes.c_uint64), ("bgzf_blocks", ctypes.c_uint64), ("bgzf_stored", ctypes.c_uint64),
+                ("bam_ms", ctypes.c_double), ("bam_bytes", ctypes.c_uint64)]
 
 
 def shard_range(path, shard, nshards):
@@ -91,7 +92,7 @@ def snappy_decompress(data):
 # the 28-byte end-of-file marker of BGZF (SAM specification 4.1.2; gwa_bgzf_eof gives the same bytes)
 BGZF_EOF = bytes([0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0,
                   0, 0, 0, 0, 0, 0, 0, 0])
-OUTPUT_FORMATS = {"sam": 0, "bgzf": 1}  # GWA_OUT_SAM, GWA_OUT_BGZF
+OUTPUT_FORMATS = {"sam": 0, "bgzf": 1, "bam": 2}  # GWA_OUT_SAM, GWA_OUT_BGZF, GWA_OUT_BAM
 
 
 def bgzf_compress(data, device=None):
@@ -123,6 +124,7 @@ EXPORTS = ["gwa_config_default", "gwa_last_error", "gwa_device_count", "gwa_inde
            "gwa_batch_create", "gwa_batch_create_pairs", "gwa_align_pairs", "gwa_batch_run", "gwa_batch_stats", "gwa_batch_results", "gwa_batch_free",
            "gwa_batch_read_counters", "gwa_batch_results_range", "gwa_results_records", "gwa_batch_results_select", "gwa_batch_format",
            "gwa_batch_sam_copy", "gwa_batch_format_bgzf", "gwa_batch_results_bgzf", "gwa_bgzf_compress", "gwa_bgzf_eof",
+           "gwa_batch_format_bam", "gwa_batch_results_bam_records", "gwa_batch_results_bam", "gwa_bam_header",
            "gwa_pipeline_set_output",
            "gwa_pipeline_open", "gwa_pipeline_align", "gwa_pipeline_align_file", "gwa_pipeline_align_file_range",
            "gwa_pipeline_align_pair_files", "gwa_pipeline_align_pairs", "gwa_reads_shard_range", "gwa_pipeline_stats",
@@ -169,6 +171,10 @@ def lib():
         L.gwa_batch_results_bgzf.argtypes = [V, P(V), P(U64)]
         L.gwa_bgzf_compress.argtypes = [I, ctypes.c_char_p, U64, P(V), P(U64)]
         L.gwa_bgzf_eof.argtypes = [ctypes.c_char_p]
+        L.gwa_batch_format_bam.argtypes = [V, P(U64)]
+        L.gwa_batch_results_bam_records.argtypes = [V, P(V), P(U64)]
+        L.gwa_batch_results_bam.argtypes = [V, P(V), P(U64)]
+        L.gwa_bam_header.argtypes = [V, P(V), P(U64)]
         L.gwa_pipeline_set_output.argtypes = [V, ctypes.c_uint32]
         L.gwa_reads_parse.argtypes = [ctypes.c_char_p, U64, I, I, P(_ReadBuf), P(U64)]
         L.gwa_reads_free.argtypes = [P(_ReadBuf)]
@@ -308,6 +314,16 @@ class FMIndexOnGenome:
         s = ctypes.string_at(p, n.value).decode()
         lib().gwa_free(p)
         return s
+
+    def bam_header(self):
+        """The uncompressed BAM header of this index (bytes): magic, the sam_header() text, the contig table.
+        A BAM file is bgzf_compress(bam_header()) + each batch's blocks + BGZF_EOF."""
+        p, n = ctypes.c_void_p(), ctypes.c_uint64()
+        _check(lib().gwa_bam_header(self.h, ctypes.byref(p), ctypes.byref(n)))
+        try:
+            return ctypes.string_at(p, n.value)
+        finally:
+            lib().gwa_free(p)
 
     def close(self):
         if self.h:
@@ -499,7 +515,10 @@ class Pipeline:
     (one per GPU), SAM in input order.  indexes: FMIndexOnGenome handles, one per device."""
 
     def __init__(self, indexes, config, batch_reads=1 << 20, workers_per_device=0, output="sam"):
-        """output: what align_file / align_pair_files write, "sam" text or "bgzf" blocks (set_output)"""
+        """output: what align_file / align_pair_files write: "sam" text, "bgzf" blocks of it, or "bam" -- each
+        batch's BAM records as BGZF blocks, to be framed by bgzf_compress(index.bam_header()) and BGZF_EOF.  A
+        pipeline is opened for BAM: the caller has written a BAM header in front of what the runs write, so
+        set_output does not switch a pipeline to it."""
         if output not in OUTPUT_FORMATS:
             raise GwaError("output must be one of %s, got %r" % (", ".join(sorted(OUTPUT_FORMATS)), output))
         self.indexes = list(indexes)
@@ -511,13 +530,16 @@ class Pipeline:
         _check(lib().gwa_pipeline_open(ctypes.cast(arr, ctypes.c_void_p), len(self.indexes), ctypes.byref(c),
                                        batch_reads, workers_per_device, ctypes.byref(self.h)))
         if output != "sam":
-            self.set_output(output)
+            _check(lib().gwa_pipeline_set_output(self.h, OUTPUT_FORMATS[output]))
 
     def set_output(self, output):
-        """"sam": file runs write SAM text (the default); "bgzf": each batch's text as BGZF blocks compressed on
-        its GPU -- no header and no EOF marker (gwa_pipeline_set_output).  align_batch / align_pairs return text."""
-        if output not in OUTPUT_FORMATS:
-            raise GwaError("output must be one of %s, got %r" % (", ".join(sorted(OUTPUT_FORMATS)), output))
+        """Switch between the two forms of the SAM text: "sam", file runs write text (the default), and "bgzf",
+        each batch's text as BGZF blocks compressed on its GPU -- no header and no EOF marker
+        (gwa_pipeline_set_output).  BAM is chosen when the pipeline is opened (output="bam"), not here.
+        align_batch / align_pairs return text either way."""
+        if output not in ("sam", "bgzf"):
+            raise GwaError("set_output takes \"sam\" or \"bgzf\", got %r (BAM output is chosen when the pipeline is "
+                           "opened: Pipeline(..., output=\"bam\"))" % (output,))
         _check(lib().gwa_pipeline_set_output(self.h, OUTPUT_FORMATS[output]))
 
     def align_batch(self, reads):
@@ -647,6 +669,28 @@ class Batch:
             return ctypes.string_at(out, n.value)
         finally:
             lib().gwa_free(out)
+
+    def format_bam(self):
+        """Write the batch's BAM records (include/gwa.h) in HBM only; their size (stats(): bam_ms, bam_bytes)."""
+        n = ctypes.c_uint64()
+        _check(lib().gwa_batch_format_bam(self.h, ctypes.byref(n)))
+        return n.value
+
+    def _bam_bytes(self, fn):
+        out, n = ctypes.c_void_p(), ctypes.c_uint64()
+        _check(fn(self.h, ctypes.byref(out), ctypes.byref(n)))
+        try:
+            return ctypes.string_at(out, n.value)
+        finally:
+            lib().gwa_free(out)
+
+    def results_bam_records(self):
+        """The batch's BAM alignment records, uncompressed (bytes), built on the device."""
+        return self._bam_bytes(lib().gwa_batch_results_bam_records)
+
+    def results_bam(self):
+        """The same records as BGZF blocks (bytes, no header and no EOF marker), compressed on the device."""
+        return self._bam_bytes(lib().gwa_batch_results_bam)
 
     def stats(self):
         st = BatchStats()

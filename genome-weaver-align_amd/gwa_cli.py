@@ -4,7 +4,8 @@ A/AlignmentConfig.java:40-72, A/AlignmentScoreConfig.java:37-77).
   python genome-weaver-align_amd/gwa_cli.py bwt ref.fa            (writes ref.fa.gwa.idx)
   python genome-weaver-align_amd/gwa_cli.py align -r ref.fa [-q SEQ | reads.fq[.gz|.snap] | reads.fa[.gz|.snap]]
          [-k 0.1] [-m bsf|sf|bd|bwa] [-R besthit|allhits|topL] [-L 5] [-g 1] [-e 4] [-s 1] [-M 1] [-N 3]
-         [-G 11] [-E 4] [-S 11] [-P 5] [-W 31] [--silent] [--devices 0,1,..] [--batch 1048576] [--md] [--bgzf]
+         [-G 11] [-E 4] [-S 11] [-P 5] [-W 31] [--silent] [--devices 0,1,..] [--batch 1048576] [--md] [--bgzf | --bam]
+         [-o FILE]
   python genome-weaver-align_amd/gwa_cli.py align -r ref.fa mates_1.fq[.gz|.snap] mates_2.fq[.gz|.snap]
          [--insert-min 210] [--insert-max 390] [--check-mate-names]       (paired-end, two SAM lines per pair)
   python genome-weaver-align_amd/gwa_cli.py align -r ref.fa --interleaved pairs.fq   (mates alternating in one file)
@@ -23,6 +24,13 @@ on its GPU (gwa_pipeline_set_output; the blocks, not the text, cross PCIe), and 
 last.  With --shard R/N shard 0 writes the header and only shard N - 1 the EOF marker, so the shard files
 concatenated in order are one valid file that decompresses to the one-process SAM.  `align(ns, out=...)`
 takes a binary stream then.  The reference has no compressed output.
+
+--bam writes BAM: the header (gwa.FMIndexOnGenome.bam_header: magic, the `@SQ` text, the contig table) as BGZF
+blocks from the host encoder, every batch's alignment records built and compressed on its GPU (include/gwa.h
+states the record as a function of the SAM line), and the EOF marker last; --shard frames the shard files as
+--bgzf does, so that they concatenate to one BAM.  -q aligns its read as one batch (gwa_batch_results_bam).
+It excludes --bgzf, combines with --md, --devices and paired input, and is not written to a terminal: give
+-o FILE or redirect stdout.  The records are in input order: sorting and indexing are left to other tools.
 
 Two read files (or one with --interleaved) are paired-end input: mate i of the first file with mate i
 of the second, two SAM lines per pair, streamed through the same pipeline on every device of
@@ -137,6 +145,10 @@ def build_parser():
     a.add_argument("--bgzf", action="store_true",
                    help="write the SAM as BGZF (blocked gzip, SAM specification 4.1), compressed on the device; "
                         "the header first, the EOF marker last")
+    a.add_argument("--bam", action="store_true",
+                   help="write BAM (SAM specification 4.2): records built and BGZF-compressed on the device, in input "
+                        "order; not together with --bgzf, and not to a terminal")
+    a.add_argument("-o", dest="out", default=None, metavar="FILE", help="write the output to FILE instead of stdout")
     a.add_argument("--device", type=int, default=0, help="GPU ordinal (one device)")
     a.add_argument("--devices", default=None, help="comma-separated GPU ordinals: one index replica per GPU")
     a.add_argument("--workers", type=int, default=3, help="host worker threads per device")
@@ -244,6 +256,11 @@ def align(ns, out=sys.stdout):
     paired = ns.query is None and (len(ns.readFiles) == 2 or ns.interleaved)
     if ns.check_mate_names and not paired:
         raise gwa.GwaError("--check-mate-names needs paired-end input (two mate files, or --interleaved)")
+    bam, bgzf = getattr(ns, "bam", False), getattr(ns, "bgzf", False)
+    if bam and bgzf:
+        raise gwa.GwaError("--bam and --bgzf exclude each other: BAM is its own BGZF file")
+    if bam and out is sys.stdout and sys.stdout.isatty():
+        raise gwa.GwaError("--bam writes binary data: give -o FILE or redirect stdout")
     cfg = config_of(ns)
     shard = shard_of(ns)
     if shard is not None and (ns.query is not None or paired):
@@ -259,17 +276,19 @@ def align(ns, out=sys.stdout):
     t0 = time.perf_counter()
     fms = load_indexes(ns.refSeq, devices)
     t1 = time.perf_counter()
-    bgzf = getattr(ns, "bgzf", False)
-    if bgzf and out is sys.stdout:
+    binary = bgzf or bam
+    if binary and out is sys.stdout:
         out = sys.stdout.buffer
     if ns.silent:
         w = lambda s: None  # noqa: E731
+    elif bam:  # (only the header goes through w)
+        w = lambda b: out.write(gwa.bgzf_compress(b))  # noqa: E731
     elif bgzf:  # (the header, or -q's few lines: the host build of the encoder)
         w = lambda s: out.write(gwa.bgzf_compress(s.encode()))  # noqa: E731
     else:
         w = out.write
     if shard is None or shard[0] == 0:
-        w(fms[0].samHeader())
+        w(fms[0].bam_header() if bam else fms[0].samHeader())
     n = 0
     t_open = 0.0
     mono0 = None
@@ -283,13 +302,23 @@ def align(ns, out=sys.stdout):
 
     try:
         if ns.query is not None:
-            w(gwa.aligner(fms[0], cfg).align_batch([("read", ns.query, None)]))
+            if bam:  # the one read as a batch, its records compressed on the device
+                qb = gwa.Batch(fms[0], cfg, reads=[("read", ns.query, None)])
+                try:
+                    qb.run()
+                    blocks = qb.results_bam()
+                finally:
+                    qb.close()
+                if not ns.silent:
+                    out.write(blocks)
+            else:
+                w(gwa.aligner(fms[0], cfg).align_batch([("read", ns.query, None)]))
             n = 1
         else:
             out.flush()
             tp = time.perf_counter()
             pipe = gwa.Pipeline(fms, cfg, batch_reads=ns.batch, workers_per_device=ns.workers,
-                                output="bgzf" if bgzf else "sam")  # pins host buffers
+                                output="bam" if bam else "bgzf" if bgzf else "sam")  # pins host buffers
             t_open = time.perf_counter() - tp
             try:
                 # --warm-passes N: N - 1 untimed passes over the file into /dev/null first (pinned buffers,
@@ -323,7 +352,7 @@ def align(ns, out=sys.stdout):
                         with tempfile.TemporaryFile() as tf:
                             n = run_file(pipe, tf.fileno())
                             tf.seek(0)
-                            out.write(tf.read() if bgzf else tf.read().decode())
+                            out.write(tf.read() if binary else tf.read().decode())
             finally:
                 t2 = time.perf_counter()  # (the SAM is written; unpinning the buffers is teardown)
                 if ns.timing and ns.sync and mono0 is not None:  # (None: a warm pass or the sync wait failed)
@@ -331,7 +360,7 @@ def align(ns, out=sys.stdout):
                 pipe.close()
         if ns.query is not None:
             t2 = time.perf_counter()
-        if bgzf and not ns.silent and (shard is None or shard[0] == shard[1] - 1):
+        if binary and not ns.silent and (shard is None or shard[0] == shard[1] - 1):
             out.write(gwa.BGZF_EOF)
             out.flush()
     finally:
@@ -361,7 +390,11 @@ def bwt(ns):
 def main(argv=None):
     ns = build_parser().parse_args(argv)
     try:
-        if ns.cmd == "align":
+        if ns.cmd == "align" and ns.out is not None:
+            with open(ns.out, "wb" if ns.bam or ns.bgzf else "w") as f:
+                n = align(ns, out=f)
+            print("[gwa] %d reads aligned" % n, file=sys.stderr)
+        elif ns.cmd == "align":
             n = align(ns)
             print("[gwa] %d reads aligned" % n, file=sys.stderr)
         elif ns.cmd == "bwt":

@@ -147,6 +147,10 @@ typedef struct {
   uint64_t bgzf_bytes;     /* its output, */
   uint64_t bgzf_blocks;    /* blocks (ceil(SAM bytes / 65280)) */
   uint64_t bgzf_stored;    /* and how many of them are stored blocks (deflate would not have been smaller) */
+  double bam_ms;           /* the last BAM record formatting of the batch on the device (gwa_batch_format_bam /
+                            * results_bam_records / results_bam; HIP events).  compress_ms and the bgzf_* fields
+                            * describe the last compression, of SAM text or of BAM records */
+  uint64_t bam_bytes;      /* its output: the uncompressed records */
 } gwa_batch_stats_t;
 
 void gwa_config_default(gwa_config_t *cfg);
@@ -238,6 +242,46 @@ int gwa_batch_results_bgzf(gwa_batch_t *b, uint8_t **out, uint64_t *len);
 int gwa_bgzf_compress(int device, const void *in, uint64_t n, uint8_t **out, uint64_t *out_len);
 /* The 28-byte end-of-file marker of the specification (an empty block). */
 int gwa_bgzf_eof(uint8_t *out28);
+/* ---- BAM output: alignment records built on the device, in the BGZF container above ----
+ * The reference has no BAM, and some lines it prints are not SAM-spec alignments, so a record is a total
+ * function of the printed SAM line (with the batch's sam_tags), as MD is.  Layout: the BAMv1 alignment record
+ * of the SAM specification section 4.2, little-endian: block_size, refID, pos, l_read_name (u8), mapq (u8),
+ * bin (u16), n_cigar_op (u16), flag (u16), l_seq (u32), next_refID, next_pos, tlen, read_name NUL, cigar, seq,
+ * qual, tags.
+ *   refID       index of the contig RNAME names; -1 for "*", the empty name and a line without a contig
+ *   next_refID  the same of RNEXT; "=" gives this line's refID; "*" gives -1 and next_pos -1
+ *   pos, next_pos  POS - 1 and PNEXT - 1 as they are (POS 0 gives -1, a negative POS keeps its two's complement)
+ *   tlen        TLEN (its low 32 bits);  mapq 1, the column the reference always prints;  flag FLAG
+ *   read_name   the QNAME bytes and a NUL (an empty name: the NUL alone).  A name longer than 254 bytes fails
+ *               the batch: "BAM: read <index> has a name of <n> bytes (at most 254 fit a record)"
+ *   cigar       the printed elements, len << 4 | op with op from MIDNSHP=X (the writer prints no '=');
+ *               an empty CIGAR and "*" give n_cigar_op 0
+ *   seq         SEQ at 4 bits per base, A 1, C 2, G 4, T 8, N 15, the first base of a byte in its high nibble,
+ *               the unused low nibble of an odd l_seq 0; an empty SEQ gives l_seq 0
+ *   qual        l_seq bytes: the QUAL bytes - 33 (mod 256) where QUAL has exactly l_seq bytes (a "*" next to a
+ *               one-base SEQ is such a byte), otherwise 0xFF each (QUAL "*", and a split record whose quality
+ *               substring and SEQ differ in length)
+ *   bin         4680 (reg2bin(-1, 0)) for FLAG 0x4 or pos < 0, else the specification's reg2bin(pos, pos +
+ *               max(reflen, 1)), reflen = the sum of the M, D, N and X elements
+ *   tags        those printed, in the printed order: NM as int32 (type i), XP as Z, X0 as int32 (type i), MD as
+ *               Z (GWA_SAM_TAG_MD, the text's value); the integer types are fixed, so a record's size does not
+ *               depend on a tag's value
+ * Where the SAM writer fails (the reference would throw), the BAM writer fails the same way.  The same batch
+ * gives the same bytes on every run, from the device and from the host build (csrc/bam_core.h).
+ * A BAM file is BGZF(gwa_bam_header) + BGZF(records of batch 0) + BGZF(records of batch 1) ... + the EOF
+ * marker; every part is its own run of blocks (a short block at its end), and records may straddle the
+ * 65 280-byte slices inside a part. */
+#define GWA_OUT_BAM 2u
+/* The batch's BAM records written in HBM only (timing counterpart of gwa_batch_format); *bam_bytes = their
+ * size.  gwa_batch_sam_copy fails afterwards: the last formatting was not gwa_batch_format's. */
+int gwa_batch_format_bam(gwa_batch_t *b, uint64_t *bam_bytes);
+/* The uncompressed records in library-owned host memory (gwa_free).  -m bd / -m bwa: no record. */
+int gwa_batch_results_bam_records(gwa_batch_t *b, uint8_t **out, uint64_t *len);
+/* The same bytes as BGZF blocks (no EOF marker), compressed on the device. */
+int gwa_batch_results_bam(gwa_batch_t *b, uint8_t **out, uint64_t *len);
+/* The uncompressed BAM header (gwa_free), built on the host: "BAM\1", l_text and the text gwa_sam_header
+ * returns, n_ref, and per contig l_name (with its NUL), the name as RNAME prints it, NUL, l_ref. */
+int gwa_bam_header(const gwa_index_t *ix, uint8_t **out, uint64_t *len);
 /* SAM for reads [first, first+count) only (n_reads = count). */
 int gwa_batch_results_range(gwa_batch_t *b, uint32_t first, uint32_t count, gwa_results_t *out);
 void gwa_batch_free(gwa_batch_t *b);
@@ -324,9 +368,11 @@ int gwa_reads_shard_range(const char *path, uint32_t shard, uint32_t nshards, ui
  * decompressed into *out (malloc'd, NUL-terminated; gwa_free).  Host only, no device needed. */
 int gwa_snappy_decompress(const uint8_t *in, uint64_t n, char **out, uint64_t *out_len);
 /* What gwa_pipeline_align_file / _file_range / _pair_files write to fd from now on: GWA_OUT_SAM (the
- * default) or GWA_OUT_BGZF -- each batch's SAM text as its own run of BGZF blocks (compressed on the
+ * default), GWA_OUT_BGZF -- each batch's SAM text as its own run of BGZF blocks (compressed on the
  * batch's device, one D2H of the blocks), in input order under the same pwrite / write rules; no header
- * and no EOF marker: the caller frames the file, as it writes the @SQ header.  gwa_pipeline_align and
+ * and no EOF marker: the caller frames the file, as it writes the @SQ header -- or GWA_OUT_BAM: each
+ * batch's BAM records as its own run of BGZF blocks under the same rules (the caller writes
+ * BGZF(gwa_bam_header) before and the EOF marker after).  gwa_pipeline_align and
  * gwa_pipeline_align_pairs return text either way.  Another value fails ("gwa_pipeline_set_output:
  * unknown format N"). */
 int gwa_pipeline_set_output(gwa_pipeline_t *p, uint32_t format);
