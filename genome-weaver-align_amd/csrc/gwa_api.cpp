@@ -20,6 +20,7 @@
 
 #include "bam_core.h"
 #include "bgzf_host.h"
+#include "inflate_host.h"
 #include "bsf_core.h"
 #include "sf_core.h"
 #include "host_index.h"
@@ -1945,6 +1946,7 @@ uint64_t batchSamInto(gwa_batch_t *b, char **buf, uint64_t *cap) {
   HIPCHK(hipStreamSynchronize(b->stream));
   return total;
 }
+int indexDevice(const gwa_index_t *ix) { return ix->device; }
 void pinnedFree(char *p) {
   if (p) (void)hipHostFree(p);
 }
@@ -2137,6 +2139,75 @@ int gwa_bgzf_compress(int device, const void *in, uint64_t n, uint8_t **out, uin
     if (p) (void)hipFree(p);
   return 0;
 }
+
+}  // extern "C"
+
+namespace gwa {
+struct DeviceInflater;  // inflate.hip
+DeviceInflater *inflaterCreate(int device);
+void inflaterFree(DeviceInflater *d);
+float inflaterKernelMs(const DeviceInflater *d);
+void inflaterRun(DeviceInflater *d, const uint8_t *comp, uint64_t n, const inflate::Member *ms, uint64_t nm, uint8_t *dst,
+                 uint64_t dstLen, int repeat);
+}  // namespace gwa
+
+// gwa_bgzf_decompress and its timed form: the walk over the members, then the kernel or the host build
+static int bgzfDecompress(int device, const uint8_t *in, uint64_t n, int repeat, uint8_t **out, uint64_t *out_len, double *kernelMs) {
+  uint8_t *res = nullptr;
+  DeviceInflater *inf = nullptr;
+  try {
+    std::vector<inflate::Member> ms;
+    std::vector<uint64_t> offs;
+    const uint64_t total = inflate::walkMembers(in, n, ms, offs);
+    res = (uint8_t *)malloc(total + 1);
+    if (!res) throw std::runtime_error("out of host memory for the inflated text");
+    uint64_t bad = ms.size();
+    uint32_t st = 0;
+    if (device < 0) {
+      std::vector<uint32_t> status(ms.size() + 1);
+      bad = inflate::inflateHost(in, n, ms.data(), ms.size(), res, total, status.data());
+      if (bad < ms.size()) st = status[bad];
+    } else {
+      inf = inflaterCreate(device);
+      try {
+        inflaterRun(inf, in, n, ms.data(), ms.size(), res, total, repeat);
+      } catch (inflate::InflateError &e) {
+        bad = e.member;
+        st = e.status;
+      }
+      if (kernelMs) *kernelMs = inflaterKernelMs(inf);
+      inflaterFree(inf);
+      inf = nullptr;
+    }
+    if (bad < ms.size())
+      throw std::runtime_error(inflate::memberLabel(bad, offs[bad]) + inflate::InflateError(bad, st).what());
+    *out = res;
+    *out_len = total;
+    return 0;
+  } catch (std::exception &e) {
+    free(res);
+    if (inf) inflaterFree(inf);
+    return fail(e.what());
+  }
+}
+
+extern "C" {
+
+int gwa_bgzf_decompress(int device, const uint8_t *in, uint64_t n, uint8_t **out, uint64_t *out_len) {
+  return bgzfDecompress(device, in, n, 1, out, out_len, nullptr);
+}
+
+int gwa_bgzf_decompress_timed(int device, const uint8_t *in, uint64_t n, int repeat, uint64_t *out_len, double *kernel_ms) {
+  uint8_t *out = nullptr;
+  if (device < 0) return fail("gwa_bgzf_decompress_timed: needs a device");
+  const int rc = bgzfDecompress(device, in, n, repeat, &out, out_len, kernel_ms);
+  free(out);
+  return rc;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int gwa_batch_sam_copy(gwa_batch_t *b, void *dst, uint64_t *len) {
   try {

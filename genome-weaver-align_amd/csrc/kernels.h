@@ -78,6 +78,13 @@ void launchBgzfBlocks(const uint8_t *in, uint64_t n, uint64_t nBlocks, void *slo
                       uint32_t *stored, hipStream_t s);
 void launchBgzfCompact(const void *slots, const uint32_t *sizes, const uint64_t *offs, uint64_t nBlocks, uint8_t *out,
                        hipStream_t s);
+// BGZF input (inflate.hip): members ms[0, nMembers) of the compressed bytes in[0, n) (16-byte aligned) inflated
+// to out + outOff, one workgroup each; status[k] = 0 or member k's error word (inflate_core.h)
+namespace inflate {
+struct Member;
+}
+void launchInflate(const uint8_t *in, uint64_t n, const inflate::Member *ms, uint64_t nMembers, uint8_t *out, uint64_t outCap,
+                   uint32_t *status, hipStream_t s);
 size_t sortSearchListTmpBytes(uint32_t n);
 void launchSortSearchList(const uint32_t *listIn, uint32_t *listOut, uint32_t *keysIn, uint32_t *keysOut, uint32_t n,
                           const ScanRes *sres, bool byKey, void *tmp, size_t tmpBytes, hipStream_t s);

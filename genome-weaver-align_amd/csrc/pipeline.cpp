@@ -63,6 +63,16 @@ uint64_t batchBgzfInto(gwa_batch_t *b, char **buf, uint64_t *cap);  // the same 
 uint64_t batchBamInto(gwa_batch_t *b, char **buf, uint64_t *cap);   // the batch's BAM records as BGZF blocks
 void pinnedFree(char *p);
 char *pinnedAlloc(uint64_t bytes);
+// BGZF read files: the kernel path of the inflater (inflate.hip), on the device of an index handle
+namespace inflate {
+struct Member;
+}
+struct DeviceInflater;
+DeviceInflater *inflaterCreate(int device);
+void inflaterFree(DeviceInflater *d);
+void inflaterRun(DeviceInflater *d, const uint8_t *comp, uint64_t n, const inflate::Member *ms, uint64_t nm, uint8_t *dst,
+                 uint64_t dstLen, int repeat);
+int indexDevice(const gwa_index_t *ix);  // gwa_api.cpp
 }
 
 namespace {
@@ -267,8 +277,22 @@ struct gwa_pipeline {
   uint64_t pinnedBufs = 0, pinnedBytes = 0;  // pinned so far (lazily, by align_file)
   std::mutex samMu;
   std::vector<std::pair<char *, uint64_t>> samBufs;  // pinned SAM buffers, one per file worker, kept too
+  // BGZF read files are inflated on the first handle's device, on a stream of the inflater's own with
+  // pooled device buffers; made by the first chunk that needs it, kept across align_file calls
+  std::mutex inflaterMu;
+  gwa::DeviceInflater *inflater = nullptr;
+  gwa::Inflater deviceInflater() {
+    return [this](const uint8_t *comp, uint64_t n, const gwa::inflate::Member *ms, uint64_t nm, char *dst, uint64_t dstLen) {
+      {
+        std::lock_guard<std::mutex> g(inflaterMu);
+        if (!inflater) inflater = gwa::inflaterCreate(gwa::indexDevice(ix[0]));
+      }
+      gwa::inflaterRun(inflater, comp, n, ms, nm, (uint8_t *)dst, dstLen, 1);
+    };
+  }
   ~gwa_pipeline() {
     for (auto &b : samBufs) gwa::pinnedFree(b.first);
+    if (inflater) gwa::inflaterFree(inflater);
   }
 };
 
@@ -907,7 +931,7 @@ uint64_t pinReadBuffers(gwa_pipeline *p, const std::vector<gwa::RecordStream *> 
 
 // the end of a file run: workers joined, the output position, the counters
 void finishFileRun(gwa_pipeline *p, Run &run, int fd, Clock::time_point t0, double readS, double frameS,
-                   uint64_t pinnedUsable) {
+                   uint64_t pinnedUsable, const std::vector<gwa::RecordStream *> &streams) {
   run.finishJobs();
   for (auto &t : run.workers) t.join();
   run.workers.clear();
@@ -929,6 +953,11 @@ void finishFileRun(gwa_pipeline *p, Run &run, int fd, Clock::time_point t0, doub
   st.write_s = run.writeS;
   st.order_wait_s = run.waitS;
   st.out_bytes = run.outBytes;
+  for (gwa::RecordStream *rs : streams) {
+    st.inflate_s += rs->inflateSeconds();
+    st.inflate_blocks += rs->inflateBlocks();
+    st.in_bytes += rs->compressedBytes();
+  }
 }
 
 }  // namespace
@@ -941,7 +970,8 @@ int gwa_pipeline_align_file_range(gwa_pipeline_t *p, const char *path, int fd, u
   try {
     // The stream's IO thread reads the file in chunks into pooled pinned buffers and this thread
     // frames them into batches of complete records (record_stream.cpp); the workers do the rest.
-    gwa::RecordStream rs(path, begin, end, p->batchReads, [p](size_t cap) { return p->pool.get(cap); });
+    gwa::RecordStream rs(path, begin, end, p->batchReads, [p](size_t cap) { return p->pool.get(cap); }, 0,
+                         p->deviceInflater());
     setOutput(run, fd);
     const uint64_t pinnedUsable = pinReadBuffers(p, {&rs});
     const auto t0 = Clock::now();
@@ -958,7 +988,7 @@ int gwa_pipeline_align_file_range(gwa_pipeline_t *p, const char *path, int fd, u
       j.starts = std::move(s.starts);
       if (!run.push(std::move(j))) break;
     }
-    finishFileRun(p, run, fd, t0, rs.readSeconds(), rs.frameSeconds(), pinnedUsable);
+    finishFileRun(p, run, fd, t0, rs.readSeconds(), rs.frameSeconds(), pinnedUsable, {&rs});
     if (n_reads) *n_reads = run.fileReads;
     return 0;
   } catch (std::exception &e) {
@@ -984,7 +1014,8 @@ int gwa_pipeline_align_pair_files(gwa_pipeline_t *p, const char *path1, const ch
     // The two mate files as zipped record streams, or one interleaved file (record_stream.cpp
     // PairedRecordStream); both streams draw their buffers from the pipeline's pool.
     const bool inter = path2 == nullptr;
-    gwa::PairedRecordStream prs(path1, path2, p->batchReads, [p](size_t cap) { return p->pool.get(cap); });
+    gwa::PairedRecordStream prs(path1, path2, p->batchReads, [p](size_t cap) { return p->pool.get(cap); },
+                                p->deviceInflater());
     setOutput(run, fd);
     const uint64_t pinnedUsable = pinReadBuffers(p, prs.streams());
     const auto t0 = Clock::now();
@@ -1009,7 +1040,7 @@ int gwa_pipeline_align_pair_files(gwa_pipeline_t *p, const char *path1, const ch
       }
       if (!run.push(std::move(j))) break;
     }
-    finishFileRun(p, run, fd, t0, prs.readSeconds(), prs.frameSeconds(), pinnedUsable);
+    finishFileRun(p, run, fd, t0, prs.readSeconds(), prs.frameSeconds(), pinnedUsable, prs.streams());
     if (n_pairs) *n_pairs = run.fileReads / 2;
     return 0;
   } catch (std::exception &e) {

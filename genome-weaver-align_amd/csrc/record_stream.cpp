@@ -14,6 +14,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include "inflate_host.h"
 #include "snappy_stream.h"
 
 namespace gwa {
@@ -29,6 +30,8 @@ double secs(Clock::time_point a, Clock::time_point b) { return std::chrono::dura
 // read-file chunks (and the room before each for the records carried over from the previous one);
 // a smaller file reads in one chunk of its own size
 constexpr uint64_t kChunk = 256ull << 20, kReserve = 512ull << 20;
+// BGZF source: compressed bytes read per pread, and the largest member (BSIZE is 16 bits)
+constexpr uint64_t kBgzfRead = 8ull << 20, kBgzfMember = 65536;
 }  // namespace
 
 int compressedKind(const char *path) {
@@ -55,6 +58,11 @@ struct RecordStream::Source {
   gzFile f = nullptr;
   std::unique_ptr<SnapReader> snap;
   int in = -1;
+  // BGZF: the file's bytes from offset cbufOff on that are not inflated yet, the next offset to read, the
+  // members handed to the inflater so far
+  std::vector<uint8_t> cbuf;
+  uint64_t cbufOff = 0, fileAt = 0, members = 0;
+  bool eof = false;
   ~Source() {
     if (f) gzclose(f);
     if (in >= 0) ::close(in);
@@ -62,19 +70,43 @@ struct RecordStream::Source {
 };
 
 RecordStream::RecordStream(const char *path, uint64_t begin, uint64_t end, uint64_t batchRecords, TextAlloc alloc,
-                           uint64_t chunkBytes)
+                           uint64_t chunkBytes, Inflater inflater)
     : path_(path), begin_(begin), end_(end), batch_(std::max<uint64_t>(1, batchRecords)), alloc_(std::move(alloc)),
-      src_(new Source()) {
+      inflater_(std::move(inflater)), src_(new Source()) {
   fmt_ = formatOf(path);
   kind_ = compressedKind(path);
   const bool whole = begin == 0 && end == ~0ull;
   if (kind_) {
     if (!whole) throw std::runtime_error(std::string("a byte range needs an uncompressed read file: ") + path);
+    if (kind_ == 1) {  // BGZF when the first member has the BC subfield (GWA_BGZF_INPUT=0: never)
+      const char *e = getenv("GWA_BGZF_INPUT");
+      if (!(e && e[0] == '0' && !e[1])) {
+        const int fd = ::open(path, O_RDONLY);
+        if (fd < 0) throw std::runtime_error(std::string("cannot open ") + path);
+        std::vector<uint8_t> head(kBgzfMember);
+        uint64_t got = 0;
+        for (;;) {
+          const ssize_t r = ::pread(fd, head.data() + got, head.size() - got, (off_t)got);
+          if (r <= 0) break;
+          got += (uint64_t)r;
+          if (got == head.size()) break;
+        }
+        inflate::Member m;
+        uint32_t size = 0;
+        std::string why;
+        if (inflate::parseMember(head.data(), got, &m, &size, &why) == 1) {
+          kind_ = 3;
+          src_->in = fd;
+        } else {
+          ::close(fd);
+        }
+      }
+    }
     if (kind_ == 1) {
       src_->f = gzopen(path, "rb");
       if (!src_->f) throw std::runtime_error(std::string("cannot open ") + path);
       gzbuffer(src_->f, 1u << 20);
-    } else {
+    } else if (kind_ == 2) {
       src_->snap.reset(new SnapReader(path));
     }
   } else {
@@ -94,6 +126,7 @@ RecordStream::RecordStream(const char *path, uint64_t begin, uint64_t end, uint6
   // carry paths
   if (const char *e = getenv("GWA_PIPE_CHUNK"))
     if (strtoull(e, nullptr, 10) > 0) chunk_ = strtoull(e, nullptr, 10);
+  if (kind_ == 3) chunk_ = std::max<uint64_t>(chunk_, kBgzfMember);  // (any member fits an empty chunk)
   reserve_ = std::min<uint64_t>(kReserve, 2 * chunk_);
 }
 
@@ -114,6 +147,85 @@ double RecordStream::readSeconds() {
   return readS_;
 }
 
+double RecordStream::inflateSeconds() {
+  std::lock_guard<std::mutex> g(qmu_);
+  return inflateS_;
+}
+uint64_t RecordStream::inflateBlocks() {
+  std::lock_guard<std::mutex> g(qmu_);
+  return inflateBlocks_;
+}
+uint64_t RecordStream::compressedBytes() {
+  std::lock_guard<std::mutex> g(qmu_);
+  return compBytes_;
+}
+
+// BGZF source: whole members into dst while their ISIZEs fit `chunk`, inflated by one call
+bool RecordStream::readBgzfChunk(char *dst, uint64_t chunk, uint64_t *got) {
+  Source &S = *src_;
+  std::vector<inflate::Member> ms;
+  std::vector<uint64_t> offs;  // the members' offsets in the file
+  uint64_t cur = 0, text = 0, readNow = 0;
+  bool fileEnd = false;
+  for (;;) {
+    // a member is at most 65 536 bytes: with that many in the buffer, or the file's end, it is whole
+    while (!S.eof && S.cbuf.size() - cur < kBgzfMember) {
+      const size_t at = S.cbuf.size();
+      S.cbuf.resize(at + kBgzfRead);
+      const ssize_t r = ::pread(S.in, S.cbuf.data() + at, kBgzfRead, (off_t)S.fileAt);
+      if (r < 0) throw std::runtime_error(std::string("read error: ") + path_);
+      S.cbuf.resize(at + (size_t)r);
+      S.fileAt += (uint64_t)r;
+      readNow += (uint64_t)r;
+      if (r == 0) S.eof = true;
+    }
+    const uint64_t avail = S.cbuf.size() - cur;
+    if (avail == 0) {
+      fileEnd = true;
+      break;
+    }
+    inflate::Member m;
+    uint32_t size = 0;
+    std::string why;
+    const int r = inflate::parseMember(S.cbuf.data() + cur, avail, &m, &size, &why);
+    const std::string label = path_ + ": " + inflate::memberLabel(S.members + ms.size(), S.cbufOff + cur);
+    if (r < 0) throw std::runtime_error(label + why);
+    if (r == 0) throw std::runtime_error(label + "the file ends inside the member (" + std::to_string(avail) + " bytes left)");
+    if (text + m.isize > chunk) break;
+    m.payOff += cur;
+    m.outOff = text;
+    offs.push_back(S.cbufOff + cur);
+    ms.push_back(m);
+    text += m.isize;
+    cur += size;
+  }
+  const auto t0 = Clock::now();
+  try {
+    if (inflater_) {
+      inflater_(S.cbuf.data(), cur, ms.data(), ms.size(), dst, text);
+    } else {
+      std::vector<uint32_t> status(ms.size() + 1);
+      const uint64_t bad = inflate::inflateHost(S.cbuf.data(), cur, ms.data(), ms.size(), (uint8_t *)dst, text, status.data());
+      if (bad < ms.size()) throw inflate::InflateError(bad, status[bad]);
+    }
+  } catch (inflate::InflateError &e) {
+    const uint64_t k = std::min<uint64_t>(e.member, ms.size() - 1);
+    throw std::runtime_error(path_ + ": " + inflate::memberLabel(S.members + k, offs[k]) + e.what());
+  }
+  const double is = secs(t0, Clock::now());
+  {
+    std::lock_guard<std::mutex> g(qmu_);
+    inflateS_ += is;
+    if (inflater_) inflateBlocks_ += ms.size();
+    compBytes_ += readNow;
+  }
+  S.cbuf.erase(S.cbuf.begin(), S.cbuf.begin() + (long)cur);
+  S.cbufOff += cur;
+  S.members += ms.size();
+  *got = text;
+  return fileEnd;
+}
+
 void RecordStream::ioLoop() {
   const uint64_t chunk = chunk_, reserve = reserve_, end = end_;
   const bool gz = kind_ != 0;
@@ -129,7 +241,10 @@ void RecordStream::ioLoop() {
       c.buf = alloc_(reserve + chunk);
       const auto r0 = Clock::now();
       char *dst = c.buf->p + reserve;
-      if (src_->snap) {
+      bool bgzfEnd = false;
+      if (kind_ == 3) {
+        bgzfEnd = readBgzfChunk(dst, chunk, &c.got);
+      } else if (src_->snap) {
         c.got = src_->snap->read(dst, chunk);
       } else if (gz) {
         while (c.got < chunk) {
@@ -167,7 +282,8 @@ void RecordStream::ioLoop() {
         ::lseek(in, at + (off_t)c.got, SEEK_SET);
         if ((uint64_t)at + c.got >= end) c.got = std::min<uint64_t>(c.got, end - (uint64_t)at);
       }
-      c.final = c.got < chunk || (!gz && (uint64_t)::lseek(in, 0, SEEK_CUR) >= end);
+      // (a BGZF chunk ends before the member that does not fit: short, but not the file's last)
+      c.final = kind_ == 3 ? bgzfEnd : c.got < chunk || (!gz && (uint64_t)::lseek(in, 0, SEEK_CUR) >= end);
       const double rs = secs(r0, Clock::now());
       std::lock_guard<std::mutex> g(qmu_);
       readS_ += rs;
@@ -322,10 +438,11 @@ bool RecordStream::next(RecordSlice *out) {
   return true;
 }
 
-PairedRecordStream::PairedRecordStream(const char *path1, const char *path2, uint64_t batchPairs, TextAlloc alloc) {
+PairedRecordStream::PairedRecordStream(const char *path1, const char *path2, uint64_t batchPairs, TextAlloc alloc,
+                                       Inflater inflater) {
   const uint64_t B = std::max<uint64_t>(1, batchPairs);
-  a_.reset(new RecordStream(path1, 0, ~0ull, path2 ? B : 2 * B, alloc));
-  if (path2) b_.reset(new RecordStream(path2, 0, ~0ull, B, alloc));
+  a_.reset(new RecordStream(path1, 0, ~0ull, path2 ? B : 2 * B, alloc, 0, inflater));
+  if (path2) b_.reset(new RecordStream(path2, 0, ~0ull, B, alloc, 0, inflater));
 }
 
 bool PairedRecordStream::next(RecordSlice *m1, RecordSlice *m2, uint64_t *pairs) {

@@ -27,6 +27,16 @@ struct TextBuf {
 // buffer has been handed out
 using TextAlloc = std::function<std::shared_ptr<TextBuf>(size_t cap)>;
 
+namespace inflate {
+struct Member;  // inflate_core.h: a BGZF member's payload and where its text goes
+}
+// Inflates the members m[0, n) of comp[0, compLen) (payload offsets relative to comp) to dst + outOff;
+// dstLen = the sum of their ISIZEs.  Throws inflate::InflateError (inflate_host.h) for a member the
+// decoder refuses.  The pipeline passes one that runs the kernel (inflate.hip); without one the stream
+// uses the host build of the same decoder.
+using Inflater = std::function<void(const uint8_t *comp, uint64_t compLen, const inflate::Member *m, uint64_t n,
+                                    char *dst, uint64_t dstLen)>;
+
 // 1: gzip (.gz), 2: snappy-java (.snap, R/ReadReaderFactory.java:130-139), 0: plain
 int compressedKind(const char *path);
 // 0: FASTA (.fa .fasta .fan), 1: FASTQ (.fastq .fq), below an optional .gz / .snap; throws otherwise
@@ -41,6 +51,13 @@ struct RecordSlice {
   std::vector<uint64_t> starts;
 };
 
+// A .gz file whose first member is a BGZF member (a gzip member with the BC subfield) is a BGZF source,
+// kind 3 (GWA_BGZF_INPUT=0 keeps it on the zlib path): the IO thread reads compressed bytes with pread,
+// walks the members' headers, fills a chunk with whole members while their ISIZEs fit it and has them
+// inflated by one call of the inflater.  Its chunks are at least 65 536 bytes, so any member fits one.  A
+// later member that is not BGZF, and a truncated last member, are errors with the member's byte offset;
+// a missing EOF marker is not.
+//
 // The file's records in order, in slices of exactly batchRecords records (the last one may be
 // shorter).  An IO thread (started by the first next()) reads -- and decompresses -- the file in
 // chunks into buffers from `alloc`, behind `reserve` bytes of room where the records carried over
@@ -52,7 +69,7 @@ class RecordStream {
   // compressed file takes no other).  chunkBytes = 0: 256 MB, or the file's size when it is smaller
   // (GWA_PIPE_CHUNK, a test knob, overrides both).
   RecordStream(const char *path, uint64_t begin, uint64_t end, uint64_t batchRecords, TextAlloc alloc,
-               uint64_t chunkBytes = 0);
+               uint64_t chunkBytes = 0, Inflater inflater = nullptr);
   ~RecordStream();
   RecordStream(const RecordStream &) = delete;
   RecordStream &operator=(const RecordStream &) = delete;
@@ -68,6 +85,12 @@ class RecordStream {
   uint64_t fileBytes() const { return fileBytes_; }        // 0 = unknown (compressed, or not a regular file)
   double readSeconds();
   double frameSeconds() const { return frameS_; }
+  // BGZF source: the time inside the inflater (a part of readSeconds), the members inflated by the
+  // caller's inflater (0 with the host build) and the compressed bytes read
+  bool bgzf() const { return kind_ == 3; }
+  double inflateSeconds();
+  uint64_t inflateBlocks();
+  uint64_t compressedBytes();
 
  private:
   struct Chunk {
@@ -75,8 +98,9 @@ class RecordStream {
     uint64_t got = 0;
     bool final = false;
   };
-  struct Source;  // the open file (plain descriptor, gzFile or SnapReader)
+  struct Source;  // the open file (plain descriptor, gzFile, SnapReader or BGZF state)
   void ioLoop();
+  bool readBgzfChunk(char *dst, uint64_t chunk, uint64_t *got);  // true: the file has ended
   void stopIo();
   bool frameNextChunk();
 
@@ -84,6 +108,7 @@ class RecordStream {
   int fmt_ = 1, kind_ = 0;
   uint64_t begin_ = 0, end_ = ~0ull, batch_ = 1, chunk_ = 0, reserve_ = 0, fileBytes_ = 0;
   TextAlloc alloc_;
+  Inflater inflater_;
   std::unique_ptr<Source> src_;
   // IO thread and its queue (at most two chunks read ahead)
   std::thread io_;
@@ -92,7 +117,8 @@ class RecordStream {
   std::deque<Chunk> q_;
   bool started_ = false, ioDone_ = false, stop_ = false;
   std::string ioErr_;
-  double readS_ = 0, frameS_ = 0;
+  double readS_ = 0, frameS_ = 0, inflateS_ = 0;
+  uint64_t inflateBlocks_ = 0, compBytes_ = 0;
   // framing state: the records carried over, the slices of the current chunk not yet handed out
   std::shared_ptr<TextBuf> prev_;
   uint64_t carryFrom_ = 0, carryLen_ = 0;
@@ -108,7 +134,7 @@ class RecordStream {
 // longer, by any count -- and when an interleaved file holds an odd number.
 class PairedRecordStream {
  public:
-  PairedRecordStream(const char *path1, const char *path2, uint64_t batchPairs, TextAlloc alloc);
+  PairedRecordStream(const char *path1, const char *path2, uint64_t batchPairs, TextAlloc alloc, Inflater inflater = nullptr);
   // the next `*pairs` pairs: mate 1 in *m1 and mate 2 in *m2, or both alternating in *m1 (interleaved;
   // *m2 is left empty); false at the end of the input
   bool next(RecordSlice *m1, RecordSlice *m2, uint64_t *pairs);

@@ -107,12 +107,34 @@ def bgzf_compress(data, device=None):
         lib().gwa_free(out)
 
 
+def bgzf_decompress(data, device=None):
+    """the text of a concatenation of BGZF members (include/gwa.h gwa_bgzf_decompress): inflated on GPU
+    `device`, or with device=None (or a negative device) by the host build of the same decoder; bytes and
+    errors are identical.  A malformed member raises with its index, byte offset and what was wrong."""
+    data = bytes(data)
+    out, n = ctypes.c_void_p(), ctypes.c_uint64()
+    _check(lib().gwa_bgzf_decompress(-1 if device is None else device, data, len(data), ctypes.byref(out), ctypes.byref(n)))
+    try:
+        return ctypes.string_at(out, n.value)
+    finally:
+        lib().gwa_free(out)
+
+
+def bgzf_decompress_timed(data, device=0, repeat=3):
+    """(text bytes, milliseconds of the last of `repeat` kernel launches over data resident in HBM)"""
+    data = bytes(data)
+    n, ms = ctypes.c_uint64(), ctypes.c_double()
+    _check(lib().gwa_bgzf_decompress_timed(device, data, len(data), repeat, ctypes.byref(n), ctypes.byref(ms)))
+    return n.value, ms.value
+
+
 class PipelineStats(ctypes.Structure):
     _fields_ = [("reads", ctypes.c_uint64), ("batches", ctypes.c_uint64), ("wall_s", ctypes.c_double),
                 ("read_s", ctypes.c_double), ("device_kernel_s", ctypes.c_double * 16), ("parse_s", ctypes.c_double),
                 ("setup_s", ctypes.c_double), ("format_s", ctypes.c_double), ("write_s", ctypes.c_double),
                 ("order_wait_s", ctypes.c_double), ("frame_s", ctypes.c_double), ("pinned_bufs", ctypes.c_uint64),
-                ("out_bytes", ctypes.c_uint64)]
+                ("out_bytes", ctypes.c_uint64), ("inflate_s", ctypes.c_double), ("inflate_blocks", ctypes.c_uint64),
+                ("in_bytes", ctypes.c_uint64)]
 
 
 _lib = None
@@ -124,6 +146,7 @@ EXPORTS = ["gwa_config_default", "gwa_last_error", "gwa_device_count", "gwa_inde
            "gwa_batch_create", "gwa_batch_create_pairs", "gwa_align_pairs", "gwa_batch_run", "gwa_batch_stats", "gwa_batch_results", "gwa_batch_free",
            "gwa_batch_read_counters", "gwa_batch_results_range", "gwa_results_records", "gwa_batch_results_select", "gwa_batch_format",
            "gwa_batch_sam_copy", "gwa_batch_format_bgzf", "gwa_batch_results_bgzf", "gwa_bgzf_compress", "gwa_bgzf_eof",
+           "gwa_bgzf_decompress", "gwa_bgzf_decompress_timed",
            "gwa_batch_format_bam", "gwa_batch_results_bam_records", "gwa_batch_results_bam", "gwa_bam_header",
            "gwa_pipeline_set_output",
            "gwa_pipeline_open", "gwa_pipeline_align", "gwa_pipeline_align_file", "gwa_pipeline_align_file_range",
@@ -171,6 +194,8 @@ def lib():
         L.gwa_batch_results_bgzf.argtypes = [V, P(V), P(U64)]
         L.gwa_bgzf_compress.argtypes = [I, ctypes.c_char_p, U64, P(V), P(U64)]
         L.gwa_bgzf_eof.argtypes = [ctypes.c_char_p]
+        L.gwa_bgzf_decompress.argtypes = [I, ctypes.c_char_p, U64, P(V), P(U64)]
+        L.gwa_bgzf_decompress_timed.argtypes = [I, ctypes.c_char_p, U64, I, P(U64), P(ctypes.c_double)]
         L.gwa_batch_format_bam.argtypes = [V, P(U64)]
         L.gwa_batch_results_bam_records.argtypes = [V, P(V), P(U64)]
         L.gwa_batch_results_bam.argtypes = [V, P(V), P(U64)]

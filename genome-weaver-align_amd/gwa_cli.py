@@ -348,6 +348,10 @@ def align(ns, out=sys.stdout):
                                   % (st.wall_s, st.read_s, st.frame_s, ns.workers * len(devices), st.parse_s, st.setup_s,
                                      "/".join("%.2f" % st.device_kernel_s[i] for i in range(len(devices))),
                                      st.format_s, st.write_s, st.order_wait_s, st.out_bytes), file=sys.stderr)
+                            if st.inflate_blocks or st.in_bytes:
+                                print("[gwa] BGZF input: %d compressed bytes read, %d members inflated on the device, "
+                                      "inflate %.2fs (a part of read)" % (st.in_bytes, st.inflate_blocks, st.inflate_s),
+                                      file=sys.stderr)
                     else:  # an in-memory stream (tests): through a temporary file
                         with tempfile.TemporaryFile() as tf:
                             n = run_file(pipe, tf.fileno())

@@ -242,6 +242,27 @@ int gwa_batch_results_bgzf(gwa_batch_t *b, uint8_t **out, uint64_t *len);
 int gwa_bgzf_compress(int device, const void *in, uint64_t n, uint8_t **out, uint64_t *out_len);
 /* The 28-byte end-of-file marker of the specification (an empty block). */
 int gwa_bgzf_eof(uint8_t *out28);
+/* ---- BGZF input: the same container inflated on the device ----
+ * The input is any concatenation of BGZF members (what gwa_bgzf_compress, bgzip and htslib write): a gzip
+ * member with CM 8 and FLG = FEXTRA whose extra field holds a BC subfield of length 2 (other subfields may
+ * stand before or after it) with BSIZE = the member's size - 1, a raw deflate payload, CRC32 and ISIZE <=
+ * 65 536.  Empty members -- the 28-byte EOF marker among them -- may stand anywhere.  The payload may be any
+ * deflate stream: any number of stored, fixed and dynamic blocks, codes of up to 15 bits, lengths 3-258,
+ * distances 1-32 768 that never reach before the member's own output.  The headers are walked on the host;
+ * each payload is inflated by one workgroup (device >= 0) or by the host build of the same decoder (device
+ * < 0, no GPU needed), which also checks that exactly ISIZE bytes come out and that their CRC32 is the
+ * trailer's.  Both give identical bytes and identical errors.  No access of the decoder depends on the
+ * payload being well formed: a malformed member ends the call with a negative status and gwa_last_error()
+ * = "BGZF member <index> at byte <offset in the input>: <what was wrong>"; for a payload the decoder refused,
+ * <what> ends in "at payload bit <offset> (status <code>)" with the codes 1 reserved block type, 2 stored
+ * LEN/NLEN mismatch, 3 payload ends inside a block, 4 HLIT > 286 or HDIST > 30, 5 invalid code-length code,
+ * 6 bad code-length repeat, 7 no end-of-block code, 8 over-subscribed or incomplete code set, 9 invalid code
+ * or symbol, 10 distance before the member's output, 11 length differs from ISIZE, 12 CRC32 mismatch.
+ * The result is library-owned (gwa_free).  The reference reads .gz input with java.util.zip on one thread. */
+int gwa_bgzf_decompress(int device, const uint8_t *in, uint64_t n, uint8_t **out, uint64_t *out_len);
+/* For timing the kernel alone: the same with the compressed bytes resident in HBM and the kernel launched
+ * `repeat` times; *kernel_ms = the last launch between HIP events.  The text is discarded. */
+int gwa_bgzf_decompress_timed(int device, const uint8_t *in, uint64_t n, int repeat, uint64_t *out_len, double *kernel_ms);
 /* ---- BAM output: alignment records built on the device, in the BGZF container above ----
  * The reference has no BAM, and some lines it prints are not SAM-spec alignments, so a record is a total
  * function of the printed SAM line (with the batch's sam_tags), as MD is.  Layout: the BAMv1 alignment record
@@ -321,6 +342,11 @@ typedef struct {
   double frame_s;  /* reader thread: framing the text into batches of complete records */
   uint64_t pinned_bufs;  /* align_file: pinned read-text buffers large enough for this file's chunks */
   uint64_t out_bytes;    /* align_file / align_pair_files: bytes written to fd (SAM text, or BGZF blocks) */
+  /* BGZF read files (a .gz file whose first member has the BC subfield; GWA_BGZF_INPUT=0 reads it with zlib
+   * instead): the time inside the inflater (a part of read_s), the members inflated on the device and the
+   * compressed bytes read.  All zero for other input. */
+  double inflate_s;
+  uint64_t inflate_blocks, in_bytes;
 } gwa_pipeline_stats_t;
 int gwa_pipeline_open(gwa_index_t *const *ix, int n_ix, const gwa_config_t *cfg, uint32_t batch_reads,
                       int workers_per_device, gwa_pipeline_t **out);
@@ -328,7 +354,11 @@ int gwa_pipeline_open(gwa_index_t *const *ix, int n_ix, const gwa_config_t *cfg,
 int gwa_pipeline_align(gwa_pipeline_t *p, const gwa_reads_t *reads, gwa_results_t *out);
 /* A FASTA / FASTQ file (.fa .fasta .fan .fastq .fq, optionally .gz or .snap; ReadReaderFactory.createReader,
  * R/ReadReaderFactory.java:126-151) streamed through the devices; SAM records (no header) are
- * written to fd in input order.  *n_reads = reads aligned. */
+ * written to fd in input order.  *n_reads = reads aligned.  A .gz file whose first member is a BGZF member
+ * is inflated on the pipeline's first device, a chunk of whole members per kernel launch (BGZF input
+ * above); a later member that is not BGZF, or a truncated last member, fails the run with its byte offset
+ * (a missing EOF marker does not).  Any other .gz file is read with zlib on the IO thread.  The SAM is
+ * byte for byte the plain file's either way. */
 int gwa_pipeline_align_file(gwa_pipeline_t *p, const char *path, int fd, uint64_t *n_reads);
 /* The same over the bytes [begin, end) of a plain (not .gz / .snap) read file, which must start at a record
  * (gwa_reads_shard_range gives such ranges). */
