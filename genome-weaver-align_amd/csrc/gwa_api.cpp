@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,6 +20,8 @@
 #include <vector>
 
 #include "bam_core.h"
+#include "bam_sort.h"
+#include "bam_sorter.h"
 #include "bgzf_host.h"
 #include "inflate_host.h"
 #include "bsf_core.h"
@@ -354,6 +357,8 @@ struct gwa_batch {
   RescueOut *d_rescue = nullptr;  // paired-end: per pair, the pair choice and mate rescue (pair_rescue_kernel)
   uint32_t *d_heavy = nullptr;     // paired-end: [pairs] heavy-pair list + its count (pair_choose_kernel)
   std::vector<std::pair<uint32_t, int>> deep;  // (read, tier) of every read rerun on a tier >= 1
+  gwa::BamSortBuf *sortBuf = nullptr;  // the buffers of the batch's coordinate sorts (bam_sort.hip)
+  gwa_bam_sort_times_t sortTimes{};    // of the last one
 };
 
 static void freeIndexDev(gwa_index *ix) {
@@ -721,6 +726,8 @@ static void freeBatchDev(gwa_batch *b) {
                 b->d_bgzSlots, b->d_bgzOut, b->d_bgzSizes, b->d_bgzStored, b->d_bgzOffs};
   if (b->stream) (void)hipStreamSynchronize(b->stream);  // (then every buffer below is idle)
   for (void *p : ps) batchFree(p, nullptr);
+  bamSortFree(b->sortBuf);
+  b->sortBuf = nullptr;
   // the text blobs (one allocation may back several of them)
   char *tx[3] = {b->d_seqText, b->d_nameText, b->d_qualText};
   for (int i = 0; i < 3; ++i) {
@@ -2086,6 +2093,144 @@ int gwa_bam_header(const gwa_index_t *ix, uint8_t **out, uint64_t *len) {
     return fail(e.what());
   }
 }
+
+// the whole batch's BAM records formatted (bamOnDevice) and put into coordinate order in HBM (bam_sort.hip)
+static void bamSortedOnDevice(gwa_batch_t *b, BamSortResult *r) {
+  const uint64_t total = bamOnDevice(b);
+  b->sortTimes = gwa_bam_sort_times_t{};
+  *r = BamSortResult{};
+  if (!total) return;
+  if (!b->sortBuf) b->sortBuf = bamSortCreate();
+  bamSortRun(b->sortBuf, (const uint8_t *)b->d_fmtText, total, total, b->d_fmtOff, b->pairs ? b->pairs : b->n, b->stream, r);
+  b->sortTimes.walk_ms = r->walk_ms;
+  b->sortTimes.sort_ms = r->sort_ms;
+  b->sortTimes.permute_ms = r->permute_ms;
+  b->sortTimes.gather_ms = r->gather_ms;
+  b->sortTimes.records = r->records;
+  b->sortTimes.bytes = r->bytes;
+}
+
+int gwa_batch_format_bam_sorted(gwa_batch_t *b, uint64_t *bytes, uint64_t *n_records) {
+  try {
+    BamSortResult r;
+    bamSortedOnDevice(b, &r);
+    *bytes = r.bytes;
+    *n_records = r.records;
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+int gwa_batch_results_bam_sorted(gwa_batch_t *b, uint8_t **records, uint64_t *len, uint64_t **keys, uint64_t *n_records) {
+  uint8_t *rec = nullptr, *k = nullptr;
+  try {
+    BamSortResult r;
+    bamSortedOnDevice(b, &r);
+    uint64_t kl = 0;
+    copyOut(b, r.d_sorted, r.bytes, "the sorted BAM records", &rec, len);
+    copyOut(b, r.d_keys, r.records * sizeof(uint64_t), "the sort keys", &k, &kl);
+    *records = rec;
+    *keys = (uint64_t *)k;
+    *n_records = r.records;
+    return 0;
+  } catch (std::exception &e) {
+    free(rec);
+    free(k);
+    return fail(e.what());
+  }
+}
+
+int gwa_batch_bam_sort_times(gwa_batch_t *b, gwa_bam_sort_times_t *t) {
+  *t = b->sortTimes;
+  return 0;
+}
+
+int gwa_bam_header_sorted(const gwa_index_t *ix, uint8_t **out, uint64_t *len) {
+  try {
+    const std::string h = bamsort::sortedHeader(bamHeader(ix->host));
+    uint8_t *p = (uint8_t *)malloc(h.size() + 1);
+    if (!p) throw std::runtime_error("out of host memory for the BAM header");
+    memcpy(p, h.data(), h.size());
+    *out = p;
+    *len = h.size();
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+struct gwa_bam_sorter {
+  gwa::BamSorter s;
+  gwa_bam_sorter(const gwa_index_t *ix, int device, const char *tmp, uint64_t mem)
+      : s(ix->host.names, std::vector<int64_t>(ix->host.lengths.begin(), ix->host.lengths.end()), device, tmp, mem) {}
+};
+
+int gwa_bam_sorter_open(const gwa_index_t *ix, int device, const char *tmp_dir, uint64_t mem_bytes, gwa_bam_sorter_t **out) {
+  try {
+    *out = new gwa_bam_sorter(ix, device, tmp_dir, mem_bytes);
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+int gwa_bam_sorter_add_batch(gwa_bam_sorter_t *s, uint64_t run_id, gwa_batch_t *b) {
+  try {
+    const auto t0 = std::chrono::steady_clock::now();
+    BamSortResult r;
+    bamSortedOnDevice(b, &r);
+    std::vector<uint8_t> bytes(r.bytes);
+    std::vector<bamsort::BamRecInfo> info(r.records);
+    if (r.records) {
+      HIPCHK(hipMemcpyAsync(bytes.data(), r.d_sorted, r.bytes, hipMemcpyDeviceToHost, b->stream));
+      HIPCHK(hipMemcpyAsync(info.data(), r.d_info, r.records * sizeof(bamsort::BamRecInfo), hipMemcpyDeviceToHost, b->stream));
+      HIPCHK(hipStreamSynchronize(b->stream));
+    }
+    s->s.addSeconds(std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    s->s.addSortedRun(run_id, std::move(bytes), std::move(info));
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+int gwa_bam_sorter_add_records(gwa_bam_sorter_t *s, uint64_t run_id, const uint8_t *bytes, uint64_t len) {
+  try {
+    s->s.addRecords(run_id, bytes, len);
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+int gwa_bam_sorter_finish(gwa_bam_sorter_t *s, int fd_bam, int fd_bai, gwa_bam_sorter_stats_t *st) {
+  try {
+    BamSorterStats x;
+    s->s.finish(fd_bam, fd_bai, &x);
+    if (st) {
+      st->records = x.records;
+      st->bytes = x.bytes;
+      st->runs = x.runs;
+      st->spilled_runs = x.spilled_runs;
+      st->spilled_bytes = x.spilled_bytes;
+      st->blocks = x.blocks;
+      st->out_bytes = x.out_bytes;
+      st->bai_bytes = x.bai_bytes;
+      st->add_s = x.add_s;
+      st->order_s = x.order_s;
+      st->copy_s = x.copy_s;
+      st->compress_s = x.compress_s;
+      st->write_s = x.write_s;
+      st->index_s = x.index_s;
+    }
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+void gwa_bam_sorter_close(gwa_bam_sorter_t *s) { delete s; }
 
 int gwa_bgzf_eof(uint8_t *out28) {
   bgzf::eofMarker(out28);

@@ -273,6 +273,12 @@ struct gwa_pipeline {
   int workersPerDevice = 2;
   gwa_pipeline_stats_t stats{};
   uint32_t outFormat = GWA_OUT_SAM;  // what file runs write (gwa_pipeline_set_output)
+  // coordinate-sorted BAM (gwa_pipeline_set_sort): every file call is one sort scope
+  bool sortOn = false, sortHasTmp = false;
+  std::string sortTmp;
+  uint64_t sortMem = 0;
+  int sortBaiFd = -1;
+  gwa_bam_sorter_stats_t sortStats{};  // of the last sorted call
   BufPool pool;  // pinned read-text buffers, kept across align_file calls
   uint64_t pinnedBufs = 0, pinnedBytes = 0;  // pinned so far (lazily, by align_file)
   std::mutex samMu;
@@ -298,9 +304,18 @@ struct gwa_pipeline {
 
 namespace {
 
+// the run sorter of one sorted file call (closed with the run)
+struct SorterHold {
+  gwa_bam_sorter_t *s = nullptr;
+  ~SorterHold() {
+    if (s) gwa_bam_sorter_close(s);
+  }
+};
+
 // Shared state of one run (align or align_file).
 struct Run {
   gwa_pipeline *p;
+  SorterHold sort;  // set: the workers add their batches to it instead of writing
   std::mutex mu;
   std::condition_variable cv;
   std::deque<Job> jobs;
@@ -525,7 +540,9 @@ struct Run {
         if (rc == 0) rc = gwa_batch_run(b);
         const auto t3 = Clock::now();
         uint64_t size = 0;
-        if (rc == 0) {
+        if (rc == 0 && sort.s) {
+          rc = gwa_bam_sorter_add_batch(sort.s, j.id, b);
+        } else if (rc == 0) {
           try {
             size = p->outFormat == GWA_OUT_BAM    ? gwa::batchBamInto(b, &pinned, &cap)
                    : p->outFormat == GWA_OUT_BGZF ? gwa::batchBgzfInto(b, &pinned, &cap)
@@ -539,7 +556,7 @@ struct Run {
         gwa_batch_free(b);
         if (rc != 0) throw std::runtime_error("batch " + std::to_string(j.id) + ": " + msg);
         const auto t4 = Clock::now();
-        output(j.id, pinned, size);
+        if (!sort.s) output(j.id, pinned, size);
         outBytes += size;
         fileReads += nr;
         ++fileBatches;
@@ -730,6 +747,23 @@ int gwa_pipeline_set_output(gwa_pipeline_t *p, uint32_t format) {
   return 0;
 }
 
+int gwa_pipeline_set_sort(gwa_pipeline_t *p, const char *tmp_dir, uint64_t mem_bytes, int bai_fd) {
+  if (p->outFormat != GWA_OUT_BAM)
+    return gwa_fail_message("gwa_pipeline_set_sort: sorting needs a pipeline whose output is BAM (gwa_pipeline_set_output "
+                            "GWA_OUT_BAM)");
+  p->sortOn = true;
+  p->sortHasTmp = tmp_dir != nullptr;
+  p->sortTmp = tmp_dir ? tmp_dir : "";
+  p->sortMem = mem_bytes;
+  p->sortBaiFd = bai_fd;
+  return 0;
+}
+
+int gwa_pipeline_sort_stats(const gwa_pipeline_t *p, gwa_bam_sorter_stats_t *st) {
+  *st = p->sortStats;
+  return 0;
+}
+
 int gwa_pipeline_stats(const gwa_pipeline_t *p, gwa_pipeline_stats_t *st) {
   *st = p->stats;
   return 0;
@@ -895,6 +929,13 @@ void setOutput(Run &run, int fd) {
   const int fl = ::fcntl(fd, F_GETFL);
   run.seekable = pos0 >= 0 && fl >= 0 && !(fl & O_APPEND) && ::fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
   run.base = run.seekable ? (uint64_t)pos0 : 0;
+  gwa_pipeline *p = run.p;
+  if (p->sortOn) {  // a sort scope: the workers hand their batches to the sorter, finishFileRun writes
+    if (p->outFormat != GWA_OUT_BAM) throw std::runtime_error("gwa_pipeline_set_sort: sorting needs BAM output (GWA_OUT_BAM)");
+    if (gwa_bam_sorter_open(p->ix[0], gwa::indexDevice(p->ix[0]), p->sortHasTmp ? p->sortTmp.c_str() : nullptr, p->sortMem,
+                            &run.sort.s) != 0)
+      throw std::runtime_error(gwa_last_error());
+  }
 }
 
 // Pin the read-text buffers a run keeps in flight (read-ahead, the chunk being framed, the batches in
@@ -938,6 +979,11 @@ void finishFileRun(gwa_pipeline *p, Run &run, int fd, Clock::time_point t0, doub
   if (run.failed) throw std::runtime_error(run.err);
   if (run.nameFailId != ~0ull) throw std::runtime_error(run.nameErr);
   if (run.seekable) ::lseek(fd, (off_t)(run.base + run.nextOff), SEEK_SET);
+  if (run.sort.s) {  // the sorted stream's blocks, then the index
+    p->sortStats = gwa_bam_sorter_stats_t{};
+    if (gwa_bam_sorter_finish(run.sort.s, fd, p->sortBaiFd, &p->sortStats) != 0) throw std::runtime_error(gwa_last_error());
+    run.outBytes += p->sortStats.out_bytes;
+  }
   gwa_pipeline_stats_t &st = p->stats;
   st = gwa_pipeline_stats_t{};
   st.reads = run.fileReads;

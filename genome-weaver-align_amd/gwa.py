@@ -137,6 +137,19 @@ class PipelineStats(ctypes.Structure):
                 ("in_bytes", ctypes.c_uint64)]
 
 
+class BamSortTimes(ctypes.Structure):
+    """gwa_bam_sort_times_t: device times of a batch's last coordinate sort"""
+    _fields_ = [("walk_ms", ctypes.c_float), ("sort_ms", ctypes.c_float), ("permute_ms", ctypes.c_float),
+                ("gather_ms", ctypes.c_float), ("records", ctypes.c_uint64), ("bytes", ctypes.c_uint64)]
+
+
+class BamSorterStats(ctypes.Structure):
+    """gwa_bam_sorter_stats_t"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("records", "bytes", "runs", "spilled_runs", "spilled_bytes", "blocks",
+                                               "out_bytes", "bai_bytes")] + \
+               [(n, ctypes.c_double) for n in ("add_s", "order_s", "copy_s", "compress_s", "write_s", "index_s")]
+
+
 _lib = None
 
 # every symbol include/gwa.h declares (checked by tests/test_cabi.py)
@@ -148,6 +161,9 @@ EXPORTS = ["gwa_config_default", "gwa_last_error", "gwa_device_count", "gwa_inde
            "gwa_batch_sam_copy", "gwa_batch_format_bgzf", "gwa_batch_results_bgzf", "gwa_bgzf_compress", "gwa_bgzf_eof",
            "gwa_bgzf_decompress", "gwa_bgzf_decompress_timed",
            "gwa_batch_format_bam", "gwa_batch_results_bam_records", "gwa_batch_results_bam", "gwa_bam_header",
+           "gwa_bam_header_sorted", "gwa_batch_format_bam_sorted", "gwa_batch_results_bam_sorted", "gwa_batch_bam_sort_times",
+           "gwa_bam_sorter_open", "gwa_bam_sorter_add_batch", "gwa_bam_sorter_add_records", "gwa_bam_sorter_finish",
+           "gwa_bam_sorter_close", "gwa_pipeline_set_sort", "gwa_pipeline_sort_stats",
            "gwa_pipeline_set_output",
            "gwa_pipeline_open", "gwa_pipeline_align", "gwa_pipeline_align_file", "gwa_pipeline_align_file_range",
            "gwa_pipeline_align_pair_files", "gwa_pipeline_align_pairs", "gwa_reads_shard_range", "gwa_pipeline_stats",
@@ -200,6 +216,18 @@ def lib():
         L.gwa_batch_results_bam_records.argtypes = [V, P(V), P(U64)]
         L.gwa_batch_results_bam.argtypes = [V, P(V), P(U64)]
         L.gwa_bam_header.argtypes = [V, P(V), P(U64)]
+        if hasattr(L, "gwa_bam_header_sorted"):  # (older libraries in A/B runs lack the sorted-BAM calls)
+            L.gwa_bam_header_sorted.argtypes = [V, P(V), P(U64)]
+            L.gwa_batch_format_bam_sorted.argtypes = [V, P(U64), P(U64)]
+            L.gwa_batch_results_bam_sorted.argtypes = [V, P(V), P(U64), P(V), P(U64)]
+            L.gwa_batch_bam_sort_times.argtypes = [V, P(BamSortTimes)]
+            L.gwa_bam_sorter_open.argtypes = [V, I, ctypes.c_char_p, U64, P(V)]
+            L.gwa_bam_sorter_add_batch.argtypes = [V, U64, V]
+            L.gwa_bam_sorter_add_records.argtypes = [V, U64, ctypes.c_char_p, U64]
+            L.gwa_bam_sorter_finish.argtypes = [V, I, I, P(BamSorterStats)]
+            L.gwa_bam_sorter_close.argtypes = [V]
+            L.gwa_pipeline_set_sort.argtypes = [V, ctypes.c_char_p, U64, I]
+            L.gwa_pipeline_sort_stats.argtypes = [V, P(BamSorterStats)]
         L.gwa_pipeline_set_output.argtypes = [V, ctypes.c_uint32]
         L.gwa_reads_parse.argtypes = [ctypes.c_char_p, U64, I, I, P(_ReadBuf), P(U64)]
         L.gwa_reads_free.argtypes = [P(_ReadBuf)]
@@ -340,11 +368,12 @@ class FMIndexOnGenome:
         lib().gwa_free(p)
         return s
 
-    def bam_header(self):
+    def bam_header(self, sorted=False):
         """The uncompressed BAM header of this index (bytes): magic, the sam_header() text, the contig table.
-        A BAM file is bgzf_compress(bam_header()) + each batch's blocks + BGZF_EOF."""
+        A BAM file is bgzf_compress(bam_header()) + each batch's blocks + BGZF_EOF.  sorted: the header of a
+        coordinate-sorted file, with "@HD\tVN:1.6\tSO:coordinate" before the @SQ lines."""
         p, n = ctypes.c_void_p(), ctypes.c_uint64()
-        _check(lib().gwa_bam_header(self.h, ctypes.byref(p), ctypes.byref(n)))
+        _check((lib().gwa_bam_header_sorted if sorted else lib().gwa_bam_header)(self.h, ctypes.byref(p), ctypes.byref(n)))
         try:
             return ctypes.string_at(p, n.value)
         finally:
@@ -353,6 +382,41 @@ class FMIndexOnGenome:
     def close(self):
         if self.h:
             lib().gwa_index_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BamSorter:
+    """The run sorter of coordinate-sorted BAM output (include/gwa.h gwa_bam_sorter_*): add one run per batch
+    (add_batch) or unsorted record bytes (add_records) under run ids in input order, then finish() writes the
+    sorted stream's BGZF blocks to fd_bam and, with fd_bai, the .bai.  device < 0: the host build.  The
+    caller frames the file: bgzf_compress(index.bam_header(sorted=True)) before, BGZF_EOF after."""
+
+    def __init__(self, index, device=None, tmp_dir=None, mem=1 << 30):
+        self.h = ctypes.c_void_p()
+        dev = index.device if device is None else device
+        _check(lib().gwa_bam_sorter_open(index.h, dev, tmp_dir.encode() if tmp_dir is not None else None, mem,
+                                         ctypes.byref(self.h)))
+
+    def add_batch(self, run_id, batch):
+        _check(lib().gwa_bam_sorter_add_batch(self.h, run_id, batch.h))
+
+    def add_records(self, run_id, data):
+        _check(lib().gwa_bam_sorter_add_records(self.h, run_id, data, len(data)))
+
+    def finish(self, fd_bam, fd_bai=-1):
+        st = BamSorterStats()
+        _check(lib().gwa_bam_sorter_finish(self.h, fd_bam, fd_bai, ctypes.byref(st)))
+        return st
+
+    def close(self):
+        if self.h:
+            lib().gwa_bam_sorter_close(self.h)
             self.h = None
 
     def __del__(self):
@@ -539,11 +603,13 @@ class Pipeline:
     """Multi-device driver (include/gwa.h gwa_pipeline_*): read batches dealt to several index replicas
     (one per GPU), SAM in input order.  indexes: FMIndexOnGenome handles, one per device."""
 
-    def __init__(self, indexes, config, batch_reads=1 << 20, workers_per_device=0, output="sam"):
+    def __init__(self, indexes, config, batch_reads=1 << 20, workers_per_device=0, output="sam", sort=None):
         """output: what align_file / align_pair_files write: "sam" text, "bgzf" blocks of it, or "bam" -- each
         batch's BAM records as BGZF blocks, to be framed by bgzf_compress(index.bam_header()) and BGZF_EOF.  A
         pipeline is opened for BAM: the caller has written a BAM header in front of what the runs write, so
-        set_output does not switch a pipeline to it."""
+        set_output does not switch a pipeline to it.
+        sort: dict(tmp_dir=None, mem=1 << 30, index=None) -- with output="bam", every align_file /
+        align_pair_files call writes its records coordinate-sorted (set_sort)."""
         if output not in OUTPUT_FORMATS:
             raise GwaError("output must be one of %s, got %r" % (", ".join(sorted(OUTPUT_FORMATS)), output))
         self.indexes = list(indexes)
@@ -556,6 +622,21 @@ class Pipeline:
                                        batch_reads, workers_per_device, ctypes.byref(self.h)))
         if output != "sam":
             _check(lib().gwa_pipeline_set_output(self.h, OUTPUT_FORMATS[output]))
+        if sort is not None:
+            self.set_sort(**sort)
+
+    def set_sort(self, tmp_dir=None, mem=1 << 30, index=None):
+        """Coordinate-sorted BAM from the file calls from now on (gwa_pipeline_set_sort; a pipeline opened with
+        output="bam" only): each call is one sort scope whose sorted stream goes to its fd as BGZF blocks, to
+        be framed by bgzf_compress(index.bam_header(sorted=True)) and BGZF_EOF.  mem: bytes of records kept in
+        host memory before runs spill to files in tmp_dir; index: a file descriptor for the .bai, or None."""
+        _check(lib().gwa_pipeline_set_sort(self.h, tmp_dir.encode() if tmp_dir is not None else None, mem,
+                                           -1 if index is None else index))
+
+    def sort_stats(self):
+        st = BamSorterStats()
+        _check(lib().gwa_pipeline_sort_stats(self.h, ctypes.byref(st)))
+        return st
 
     def set_output(self, output):
         """Switch between the two forms of the SAM text: "sam", file runs write text (the default), and "bgzf",
@@ -716,6 +797,29 @@ class Batch:
     def results_bam(self):
         """The same records as BGZF blocks (bytes, no header and no EOF marker), compressed on the device."""
         return self._bam_bytes(lib().gwa_batch_results_bam)
+
+    def format_bam_sorted(self):
+        """Format and coordinate-sort the batch's BAM records in HBM only; (bytes, records)."""
+        n, r = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().gwa_batch_format_bam_sorted(self.h, ctypes.byref(n), ctypes.byref(r)))
+        return n.value, r.value
+
+    def results_bam_sorted(self):
+        """(records, keys): the batch's BAM records in coordinate order (bytes), sorted on the device, and
+        their sort keys (a list of ints, ascending; include/gwa.h "Sorted BAM")."""
+        import struct
+        out, n, keys, r = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_void_p(), ctypes.c_uint64()
+        _check(lib().gwa_batch_results_bam_sorted(self.h, ctypes.byref(out), ctypes.byref(n), ctypes.byref(keys), ctypes.byref(r)))
+        try:
+            return ctypes.string_at(out, n.value), list(struct.unpack("<%dQ" % r.value, ctypes.string_at(keys, 8 * r.value)))
+        finally:
+            lib().gwa_free(out)
+            lib().gwa_free(keys)
+
+    def bam_sort_times(self):
+        t = BamSortTimes()
+        _check(lib().gwa_batch_bam_sort_times(self.h, ctypes.byref(t)))
+        return t
 
     def stats(self):
         st = BatchStats()

@@ -30,7 +30,13 @@ blocks from the host encoder, every batch's alignment records built and compress
 states the record as a function of the SAM line), and the EOF marker last; --shard frames the shard files as
 --bgzf does, so that they concatenate to one BAM.  -q aligns its read as one batch (gwa_batch_results_bam).
 It excludes --bgzf, combines with --md, --devices and paired input, and is not written to a terminal: give
--o FILE or redirect stdout.  The records are in input order: sorting and indexing are left to other tools.
+-o FILE or redirect stdout.  The records are in input order unless --sort is given.
+
+--bam --sort writes the records in coordinate order (include/gwa.h "Sorted BAM": by refID and pos, refID -1
+last, equal keys in input order) under an "@HD VN:1.6 SO:coordinate" header: every batch is sorted on its GPU,
+the sorted runs are kept in host memory up to --sort-mem BYTES and spilled to --tmp-dir DIR beyond it, and
+merged into one BGZF stream when the input ends.  --index (with -o FILE) also writes FILE.bai.  --sort refuses
+--shard and --sync (shards would be sorted apart) and --warm-passes above 1; -q sorts its one batch.
 
 Two read files (or one with --interleaved) are paired-end input: mate i of the first file with mate i
 of the second, two SAM lines per pair, streamed through the same pipeline on every device of
@@ -148,6 +154,15 @@ def build_parser():
     a.add_argument("--bam", action="store_true",
                    help="write BAM (SAM specification 4.2): records built and BGZF-compressed on the device, in input "
                         "order; not together with --bgzf, and not to a terminal")
+    a.add_argument("--sort", action="store_true",
+                   help="with --bam: write the records in coordinate order (refID, pos; refID -1 last; equal keys in "
+                        "input order), sorted on the device, under an @HD SO:coordinate header.  Not together with "
+                        "--shard or --sync (shards would be sorted apart) and not with --warm-passes above 1, which is "
+                        "refused")
+    a.add_argument("--index", action="store_true", help="with --sort and -o FILE: write the index FILE.bai")
+    a.add_argument("--sort-mem", type=int, default=4 << 30, metavar="BYTES",
+                   help="--sort: bytes of records kept in host memory before sorted runs spill to --tmp-dir")
+    a.add_argument("--tmp-dir", default=None, metavar="DIR", help="--sort: where runs beyond --sort-mem are spilled")
     a.add_argument("-o", dest="out", default=None, metavar="FILE", help="write the output to FILE instead of stdout")
     a.add_argument("--device", type=int, default=0, help="GPU ordinal (one device)")
     a.add_argument("--devices", default=None, help="comma-separated GPU ordinals: one index replica per GPU")
@@ -261,6 +276,15 @@ def align(ns, out=sys.stdout):
         raise gwa.GwaError("--bam and --bgzf exclude each other: BAM is its own BGZF file")
     if bam and out is sys.stdout and sys.stdout.isatty():
         raise gwa.GwaError("--bam writes binary data: give -o FILE or redirect stdout")
+    sort, index = getattr(ns, "sort", False), getattr(ns, "index", False)
+    if sort and not bam:
+        raise gwa.GwaError("--sort needs --bam")
+    if index and not (sort and ns.out is not None):
+        raise gwa.GwaError("--index needs --sort and -o FILE (the index is written to FILE.bai)")
+    if sort and (ns.shard is not None or ns.sync):
+        raise gwa.GwaError("--sort does not combine with --shard or --sync: the shards would be sorted apart")
+    if sort and ns.warm_passes > 1:
+        raise gwa.GwaError("--sort does not combine with --warm-passes above 1")
     cfg = config_of(ns)
     shard = shard_of(ns)
     if shard is not None and (ns.query is not None or paired):
@@ -288,8 +312,9 @@ def align(ns, out=sys.stdout):
     else:
         w = out.write
     if shard is None or shard[0] == 0:
-        w(fms[0].bam_header() if bam else fms[0].samHeader())
+        w(fms[0].bam_header(sorted=sort) if bam else fms[0].samHeader())
     n = 0
+    bai, bai_done = None, False  # FILE.bai: opened only when an index will be written, removed when the run fails
     t_open = 0.0
     mono0 = None
 
@@ -301,12 +326,30 @@ def align(ns, out=sys.stdout):
         return pipe.align_file(ns.readFiles[0], fd, shard=shard)
 
     try:
+        if index and not ns.silent:
+            bai = open(ns.out + ".bai", "wb")
         if ns.query is not None:
             if bam:  # the one read as a batch, its records compressed on the device
                 qb = gwa.Batch(fms[0], cfg, reads=[("read", ns.query, None)])
                 try:
                     qb.run()
-                    blocks = qb.results_bam()
+                    if sort:  # its one batch through the sorter: blocks (and the index) by way of a file
+                        out.flush()
+                        sorter = gwa.BamSorter(fms[0], tmp_dir=ns.tmp_dir, mem=ns.sort_mem)
+                        try:
+                            sorter.add_batch(0, qb)
+                            if index and not ns.silent:  # (the index holds offsets of FILE: written in place)
+                                sorter.finish(out.fileno(), bai.fileno())
+                                blocks = b""
+                            else:
+                                with tempfile.TemporaryFile() as tf:
+                                    sorter.finish(tf.fileno(), -1)
+                                    tf.seek(0)
+                                    blocks = tf.read()
+                        finally:
+                            sorter.close()
+                    else:
+                        blocks = qb.results_bam()
                 finally:
                     qb.close()
                 if not ns.silent:
@@ -321,6 +364,8 @@ def align(ns, out=sys.stdout):
                                 output="bam" if bam else "bgzf" if bgzf else "sam")  # pins host buffers
             t_open = time.perf_counter() - tp
             try:
+                if sort:
+                    pipe.set_sort(tmp_dir=ns.tmp_dir, mem=ns.sort_mem, index=bai.fileno() if bai else None)
                 # --warm-passes N: N - 1 untimed passes over the file into /dev/null first (pinned buffers,
                 # device caches and the page cache warm), then the timed pass that writes the SAM
                 for _ in range(max(0, ns.warm_passes - 1)):
@@ -348,6 +393,12 @@ def align(ns, out=sys.stdout):
                                   % (st.wall_s, st.read_s, st.frame_s, ns.workers * len(devices), st.parse_s, st.setup_s,
                                      "/".join("%.2f" % st.device_kernel_s[i] for i in range(len(devices))),
                                      st.format_s, st.write_s, st.order_wait_s, st.out_bytes), file=sys.stderr)
+                            if sort:
+                                ss = pipe.sort_stats()
+                                print("[gwa] sort: %d records in %d runs (%d spilled), add %.2fs (summed over workers), order "
+                                      "%.2fs, copy %.2fs, compress %.2fs, write %.2fs, index %.2fs; %d blocks"
+                                      % (ss.records, ss.runs, ss.spilled_runs, ss.add_s, ss.order_s, ss.copy_s, ss.compress_s,
+                                         ss.write_s, ss.index_s, ss.blocks), file=sys.stderr)
                             if st.inflate_blocks or st.in_bytes:
                                 print("[gwa] BGZF input: %d compressed bytes read, %d members inflated on the device, "
                                       "inflate %.2fs (a part of read)" % (st.in_bytes, st.inflate_blocks, st.inflate_s),
@@ -367,7 +418,12 @@ def align(ns, out=sys.stdout):
         if binary and not ns.silent and (shard is None or shard[0] == shard[1] - 1):
             out.write(gwa.BGZF_EOF)
             out.flush()
+        bai_done = True
     finally:
+        if bai is not None:
+            bai.close()
+            if not bai_done:
+                os.remove(bai.name)
         for fm in fms:
             fm.close()
     if ns.timing:

@@ -303,6 +303,76 @@ int gwa_batch_results_bam(gwa_batch_t *b, uint8_t **out, uint64_t *len);
 /* The uncompressed BAM header (gwa_free), built on the host: "BAM\1", l_text and the text gwa_sam_header
  * returns, n_ref, and per contig l_name (with its NUL), the name as RNAME prints it, NUL, l_ref. */
 int gwa_bam_header(const gwa_index_t *ix, uint8_t **out, uint64_t *len);
+/* ---- Sorted BAM: the records in coordinate order, sorted on the device, and the .bai index ----
+ * The reference has nothing here; every part of the rule is a function of the record bytes alone.
+ * Order.  A record with refID >= 0 has key = (uint64)(uint32)refID << 32 | ((uint32)pos ^ 0x80000000): the
+ *   signed pos orders, pos -1 and below come first on their contig.  refID -1 has key 0xFFFFFFFF00000000
+ *   whatever its pos: such records go last.  The sorted stream is the input-order record stream stably sorted
+ *   by key: equal keys keep input order (batch order, then the order of gwa_batch_results_bam_records, so
+ *   mate 1 stays before mate 2).  The stream therefore does not depend on the batch size, the workers, the
+ *   devices, the memory limit or spilling.
+ * File.  BGZF(gwa_bam_header_sorted) + BGZF(sorted stream) + the EOF marker.  The header is gwa_bam_header's
+ *   with the line "@HD\tVN:1.6\tSO:coordinate\n" before the @SQ text.  The whole sorted stream is one text T
+ *   under the BGZF contract above (one block per 65 280-byte slice, the last one shorter), whatever parts the
+ *   writer works in.  The same records give the same file for every batch size and memory limit, from the
+ *   device and from the host build.
+ * Index (.bai, SAM specification section 5.2, little-endian): "BAI\1", n_ref, per contig its bins and its
+ *   linear index, then n_no_coor (u64).  The virtual offset of stream byte u is (H + the sizes of the blocks
+ *   before block u / 65280) << 16 | u % 65280, H = where the stream starts in the file; a record's end offset
+ *   is that at u + its size (on a slice edge: the next block, offset 0).  Indexed are the records with refID
+ *   >= 0: beg = max(pos, 0), end = min(max(pos + max(reflen, 1), beg + 1), 2^29) with reflen the sum of the
+ *   M, D, N, = and X elements, index bin = reg2bin(beg, end) (not the record's bin field).  Walking a contig's
+ *   records in stream order, every maximal run of consecutive records with one index bin is one chunk [first
+ *   record's offset, last record's end offset]; a bin's chunks stay in stream order and are not merged; bins
+ *   ascend.  Pseudo-bin 37450 is the last bin of every contig that has a record (counted in n_bin, n_chunk 2:
+ *   (first record's offset, last record's end offset), (n_mapped, n_unmapped) by FLAG 0x4).  A contig without
+ *   records has n_bin 0 and n_intv 0.  Linear index: n_intv = ((largest end - 1) >> 14) + 1, ioffset[w] = the
+ *   smallest offset of a record with beg >> 14 <= w <= (end - 1) >> 14, a window without one takes the next
+ *   later window's.  n_no_coor counts the refID -1 records.  A contig longer than 2^29 fails index creation
+ *   (the message names the contig, its length and the limit); sorting without an index still works.  No .csi. */
+int gwa_bam_header_sorted(const gwa_index_t *ix, uint8_t **out, uint64_t *len);
+/* The batch's BAM records formatted and sorted in HBM only (timing counterpart of gwa_batch_format_bam, which
+ * it includes).  Passes: a walk over each unit's block_size chain (count, scan, keys and index fields), a
+ * stable radix sort of (key, ordinal), a scan of the permuted sizes, and the gather of the records. */
+int gwa_batch_format_bam_sorted(gwa_batch_t *b, uint64_t *bytes, uint64_t *n_records);
+/* The sorted records and their keys (one per record, ascending) in library-owned host memory (gwa_free each). */
+int gwa_batch_results_bam_sorted(gwa_batch_t *b, uint8_t **records, uint64_t *len, uint64_t **keys, uint64_t *n_records);
+/* Device times of the batch's last sort (HIP events), its records and bytes. */
+typedef struct {
+  float walk_ms, sort_ms, permute_ms, gather_ms; /* walk + keys (on a batch's first sort also the allocation of
+                                                  * its buffers); radix sort; permuted sizes and their scan (with the
+                                                  * readback of the total); the gather kernel alone */
+  uint64_t records, bytes;
+} gwa_bam_sort_times_t;
+int gwa_batch_bam_sort_times(gwa_batch_t *b, gwa_bam_sort_times_t *t);
+/* The run sorter: one sorted run per batch, merged at finish.  A run is one batch's sorted records plus a
+ * per-record array of 24 bytes per record (key, size, beg, end, index bin), which always stays in host memory.
+ * run_id is the batch's number in input order; runs may be added in any order from any thread, and the result
+ * depends on the ids only.  Record bytes stay in host memory up to mem_bytes in all; beyond that a run's bytes
+ * go to a file of its own in tmp_dir (read back sequentially, unlinked at finish, close or failure); with
+ * tmp_dir NULL such an add fails, naming both numbers.  device >= 0 sorts and compresses there, device < 0 runs
+ * the host build of the same logic; identical bytes. */
+typedef struct gwa_bam_sorter gwa_bam_sorter_t;
+typedef struct {
+  uint64_t records, bytes, runs, spilled_runs, spilled_bytes, blocks, out_bytes, bai_bytes;
+  double add_s, order_s, copy_s, compress_s, write_s, index_s; /* add_s: summed over the adding threads, for
+                                                                * add_batch with the batch's formatting, sort and copy to
+                                                                * the host; the others: the stages of finish */
+} gwa_bam_sorter_stats_t;
+int gwa_bam_sorter_open(const gwa_index_t *ix, int device, const char *tmp_dir, uint64_t mem_bytes, gwa_bam_sorter_t **out);
+/* The batch's records, formatted and sorted on the batch's device, as run run_id. */
+int gwa_bam_sorter_add_batch(gwa_bam_sorter_t *s, uint64_t run_id, gwa_batch_t *b);
+/* Unsorted caller records as run run_id.  The block_size chain is validated on the host first: every
+ * block_size >= 32, name, CIGAR, SEQ and QUAL inside their record, the chain ending exactly at len; otherwise
+ * "BAM record <index> at byte <offset>: <what>". */
+int gwa_bam_sorter_add_records(gwa_bam_sorter_t *s, uint64_t run_id, const uint8_t *bytes, uint64_t len);
+/* Orders all records (a stable sort of the concatenated keys with run-major ordinals), copies them run by
+ * run, front to back, into parts of whole 65 280-byte slices, compresses each part and writes the blocks to
+ * fd_bam; then builds the index on the host and writes it to fd_bai (-1: none).  Writes neither the header nor
+ * the EOF marker; the stream's start in the file is lseek(fd_bam, 0, SEEK_CUR), so an index with a
+ * non-seekable fd_bam is refused.  No run: no block, and an index of empty contigs.  The runs are consumed. */
+int gwa_bam_sorter_finish(gwa_bam_sorter_t *s, int fd_bam, int fd_bai, gwa_bam_sorter_stats_t *stats);
+void gwa_bam_sorter_close(gwa_bam_sorter_t *s);
 /* SAM for reads [first, first+count) only (n_reads = count). */
 int gwa_batch_results_range(gwa_batch_t *b, uint32_t first, uint32_t count, gwa_results_t *out);
 void gwa_batch_free(gwa_batch_t *b);
@@ -406,6 +476,15 @@ int gwa_snappy_decompress(const uint8_t *in, uint64_t n, char **out, uint64_t *o
  * gwa_pipeline_align_pairs return text either way.  Another value fails ("gwa_pipeline_set_output:
  * unknown format N"). */
 int gwa_pipeline_set_output(gwa_pipeline_t *p, uint32_t format);
+/* Coordinate-sorted BAM ("Sorted BAM" above) from the file calls, from now on: valid only while the pipeline's
+ * output is GWA_OUT_BAM.  Each gwa_pipeline_align_file / _file_range / _pair_files call is one sort scope: the
+ * workers hand their batches to a run sorter (gwa_bam_sorter_add_batch with the batch's number, on the first
+ * handle's device; tmp_dir and mem_bytes as gwa_bam_sorter_open takes them) instead of writing, and
+ * gwa_bam_sorter_finish runs when the call ends: the sorted stream's blocks go to fd at its position, the
+ * index to bai_fd (-1: none).  The caller writes BGZF(gwa_bam_header_sorted) before and the EOF marker after.
+ * gwa_pipeline_sort_stats gives the sorter's counters and times of the last such call. */
+int gwa_pipeline_set_sort(gwa_pipeline_t *p, const char *tmp_dir, uint64_t mem_bytes, int bai_fd);
+int gwa_pipeline_sort_stats(const gwa_pipeline_t *p, gwa_bam_sorter_stats_t *st);
 int gwa_pipeline_stats(const gwa_pipeline_t *p, gwa_pipeline_stats_t *st);
 void gwa_pipeline_close(gwa_pipeline_t *p);
 
