@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "bam_core.h"
+#include "bam_in_core.h"
 #include "bam_sort.h"
 #include "bam_sorter.h"
 #include "bgzf_host.h"
@@ -1109,9 +1110,326 @@ bool batchMateNamesDiffer(gwa_batch_t *b, uint32_t *pair, std::string *name1, st
   }
   return true;
 }
+
+// ---- BAM input (include/gwa.h; kernels: bam_in.hip, per-record logic: bam_in_core.h) ----
+
+// a run of framed record bytes: where its first byte stands in the file's inflated stream (for messages)
+struct BamSeg {
+  const uint8_t *bytes;
+  uint64_t len;
+  uint64_t recIndex, byteOff;
+  const char *label;  // the file's name, or nullptr
+};
+
+// the message for the read record at g.bytes + at (its number among all records: counted along the chain)
+static std::string bamRecordError(const BamSeg &g, uint64_t at) {
+  uint64_t k = 0;
+  for (uint64_t p = 0; p < at; ++k) p += (uint64_t)bamin::ld32(g.bytes + p) + 4;
+  return (g.label ? std::string(g.label) + ": " : std::string()) + bamin::recordLabel(g.recIndex + k, g.byteOff + at) +
+         bamin::recordProblem(g.bytes + at);
+}
+
+// the bytes of the unpacked text of the n records at bytes + st[r]; every record's fields must lie in [0, len)
+// (the framing walk has seen to that; checked again, since the kernels rely on it)
+static uint64_t bamSlotBytes(const BamSeg &g, const uint64_t *st, uint32_t n) {
+  uint64_t total = 0;
+  for (uint32_t r = 0; r < n; ++r) {
+    if (st[r] > g.len || g.len - st[r] < bamin::kFixed) throw std::runtime_error("BAM input: a record start lies outside its slice");
+    const bamin::Fields f = bamin::fieldsOf(g.bytes + st[r]);
+    if (f.qual + f.lSeq > g.len - st[r]) throw std::runtime_error("BAM input: a record's fields run past its slice");
+    total += bamin::slotBytes(f);
+  }
+  return total;
+}
+
+struct BamDecoded {
+  char *dRec = nullptr, *dOut = nullptr;
+  uint64_t *fields = nullptr;
+  uint8_t *qualNull = nullptr;
+  uint32_t err[2] = {0xFFFFFFFFu, 0};  // the lowest record with a content error, the records without a quality
+};
+static void bamDecodedFree(BamDecoded *d) {
+  batchFree(d->dRec, nullptr);
+  batchFree(d->dOut, nullptr);
+  batchFree(d->fields, nullptr);
+  batchFree(d->qualNull, nullptr);
+  *d = BamDecoded();
+}
+
+// The segments copied into one allocation (segment k at segBase[k], a multiple of 16) and the n records at
+// the device offsets st[] decoded there: length pass, scan, unpack, `repeat` times (*ms: the last one
+// between events).  Synchronises the stream.
+static void bamDecodeDevice(hipStream_t s, const BamSeg *seg, int nseg, const uint64_t *segBase, const uint64_t *st, uint32_t n,
+                            uint64_t recBytes, uint64_t outBytes, int repeat, float *ms, BamDecoded *d) {
+  std::vector<void *> tmp;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  try {
+    d->dRec = bAlloc<char>(recBytes + 32);  // (+32: the chunk loads reach past a field)
+    for (int k = 0; k < nseg; ++k)
+      if (seg[k].len) HIPCHK(hipMemcpyAsync(d->dRec + segBase[k], seg[k].bytes, seg[k].len, hipMemcpyHostToDevice, s));
+    uint64_t *dStart = bAlloc<uint64_t>(n ? n : 1);
+    tmp.push_back(dStart);
+    if (n) HIPCHK(hipMemcpyAsync(dStart, st, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    d->fields = bAlloc<uint64_t>(n ? 6 * (size_t)n : 1);
+    uint64_t *dLen = bAlloc<uint64_t>((size_t)n + 1), *dOff = bAlloc<uint64_t>((size_t)n + 1);
+    tmp.push_back(dLen);
+    tmp.push_back(dOff);
+    const size_t scanBytes = bamInScanTempBytes(n);
+    void *dScan = bAlloc<uint8_t>(scanBytes);
+    tmp.push_back(dScan);
+    d->dOut = bAlloc<char>(outBytes + 32);  // (+32: the encode kernels read the text in aligned 16-B chunks)
+    d->qualNull = bAlloc<uint8_t>(n ? n : 1);
+    uint32_t *dErr = bAlloc<uint32_t>(2);
+    tmp.push_back(dErr);
+    if (ms) {
+      HIPCHK(hipEventCreate(&e0));
+      HIPCHK(hipEventCreate(&e1));
+    }
+    static const uint32_t kErrInit[2] = {0xFFFFFFFFu, 0};
+    for (int it = 0; it < std::max(1, repeat); ++it) {
+      const bool last = it + 1 >= repeat;
+      HIPCHK(hipMemcpyAsync(dErr, kErrInit, 8, hipMemcpyHostToDevice, s));
+      if (ms && last) HIPCHK(hipEventRecord(e0, s));
+      launchBamInLengths((const uint8_t *)d->dRec, dStart, n, dLen, dOff, d->fields, d->qualNull, dErr, dScan, scanBytes, s);
+      launchBamInUnpack((const uint8_t *)d->dRec, dStart, n, dOff, d->fields, d->qualNull, (uint8_t *)d->dOut, outBytes, dErr, s);
+      if (ms && last) HIPCHK(hipEventRecord(e1, s));
+    }
+    HIPCHK(hipMemcpyAsync(d->err, dErr, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (ms) HIPCHK(hipEventElapsedTime(ms, e0, e1));
+  } catch (...) {
+    (void)hipStreamSynchronize(s);
+    for (void *p : tmp) batchFree(p, nullptr);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    bamDecodedFree(d);
+    throw;
+  }
+  for (void *p : tmp) batchFree(p, nullptr);
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+}
+
+// The read text of a batch from BAM records: the segments go to HBM as they are, the names stay in them
+// (d_nameText), SEQ and QUAL are unpacked into one text behind them (d_seqText = d_qualText).  st[r] = record
+// r's device offset (segment 0 at 0, segment 1 at base2).  A record with a content error fails with the
+// message of the host build.
+static void batchInstallBam(gwa_batch *b, const BamSeg *seg, int nseg, uint64_t base2, const std::vector<uint64_t> &st,
+                            uint64_t outBytes) {
+  const uint32_t n = b->n;
+  const uint64_t segBase[2] = {0, base2};
+  const uint64_t recBytes = nseg == 2 ? base2 + seg[1].len : seg[0].len;
+  BamDecoded d;
+  bamDecodeDevice(b->stream, seg, nseg, segBase, st.data(), n, recBytes, outBytes, 1, nullptr, &d);
+  b->d_nameText = d.dRec;
+  b->d_seqText = d.dOut;
+  b->d_qualText = d.dOut;
+  b->d_fieldOwn[0] = d.fields;
+  b->d_qualNull = d.qualNull;
+  if (d.err[0] != 0xFFFFFFFFu) {
+    const uint32_t r = d.err[0];
+    if (r >= n) throw std::runtime_error("BAM input: the text of the batch does not have the size the host computed");
+    const int k = nseg == 2 && st[r] >= base2 ? 1 : 0;
+    throw std::runtime_error(bamRecordError(seg[k], st[r] - segBase[k]));
+  }
+  if (d.err[1] == 0) {  // every record has a quality
+    batchFree(b->d_qualNull, nullptr);
+    b->d_qualNull = nullptr;
+  }
+  b->hasQual = n == 0 || d.err[1] < n;
+  const uint64_t *f = d.fields;
+  b->d_nameB = f;
+  b->d_nameE = f + n;
+  b->d_seqB = f + 2 * (size_t)n;
+  b->d_seqE = f + 3 * (size_t)n;
+  b->d_qualB = f + 4 * (size_t)n;
+  b->d_qualE = f + 5 * (size_t)n;
+}
+
+// Pipeline use: a batch from the framed records bytes[0, len) of a BAM file, the n records that are reads
+// at start[] (record_stream.cpp); recIndex / byteOff: bytes[0] in the file's inflated stream.
+int batchCreateBam(gwa_index_t *ix, const gwa_config_t *cfg, const uint8_t *bytes, uint64_t len, const uint64_t *start,
+                   uint32_t n, uint64_t recIndex, uint64_t byteOff, const char *label, gwa_batch_t **out) {
+  auto *b = new gwa_batch();
+  try {
+    if (batchHead(ix, cfg, n, b)) {
+      *out = b;
+      return 0;
+    }
+    const BamSeg seg{bytes, len, recIndex, byteOff, label};
+    const uint64_t outBytes = bamSlotBytes(seg, start, n);
+    batchInstallBam(b, &seg, 1, 0, std::vector<uint64_t>(start, start + n), outBytes);
+    batchTail(b, outBytes / 2);  // (the SEQ slots, pad16(l_seq) each: the codes buffer is sized from it)
+    *out = b;
+    return 0;
+  } catch (std::exception &e) {
+    freeBatchDev(b);
+    delete b;
+    return fail(e.what());
+  }
+}
+
+// The paired form (batchCreatePairsFastq's counterpart): np mate-1 records of the first segment and np
+// mate-2 records of the second, or (bytes2 == nullptr) one segment of an interleaved file whose start1 holds
+// the np mate-1 starts and then the np mate-2 starts.  Read i is mate 1 of pair i, read np + i its mate 2.
+int batchCreatePairsBam(gwa_index_t *ix, const gwa_config_t *cfg, const uint8_t *bytes1, uint64_t len1, const uint64_t *start1,
+                        uint64_t recIndex1, uint64_t byteOff1, const uint8_t *bytes2, uint64_t len2, const uint64_t *start2,
+                        uint64_t recIndex2, uint64_t byteOff2, uint32_t np, int32_t minInsert, int32_t maxInsert,
+                        const char *label1, const char *label2, gwa_batch_t **out) {
+  auto *b = new gwa_batch();
+  try {
+    if (cfg->strategy != 0) throw std::runtime_error("paired-end alignment runs the -m bsf search");
+    if (minInsert < 0 || maxInsert < minInsert) throw std::runtime_error("bad insert-size range");
+    if (np > 0x7FFFFFFFu) throw std::runtime_error("paired-end batch too large");
+    gwa_config_t c = *cfg;
+    c.report_type = 1;  // every best hit of a mate is a pairing candidate
+    const uint32_t n = 2 * np;
+    (void)batchHead(ix, &c, n, b);  // (-m bsf: never header-only)
+    const bool two = bytes2 != nullptr;
+    const BamSeg seg[2] = {{bytes1, len1, recIndex1, byteOff1, label1}, {bytes2, len2, recIndex2, byteOff2, label2}};
+    const uint64_t base2 = two ? (len1 + 32 + 15) & ~(uint64_t)15 : 0;
+    std::vector<uint64_t> st(start1, start1 + (two ? np : n));
+    uint64_t outBytes = bamSlotBytes(seg[0], st.data(), (uint32_t)st.size());
+    if (two) {
+      outBytes += bamSlotBytes(seg[1], start2, np);
+      for (uint32_t i = 0; i < np; ++i) st.push_back(base2 + start2[i]);
+    }
+    batchInstallBam(b, seg, two ? 2 : 1, base2, st, outBytes);
+    batchTail(b, outBytes / 2);  // (the SEQ slots)
+    b->pairs = np;
+    b->minIns = minInsert;
+    b->maxIns = maxInsert;
+    b->d_rescue = bAlloc<RescueOut>(np ? np : 1);
+    b->d_heavy = bAlloc<uint32_t>((size_t)np + 2);  // list, its count, rescues skipped (window)
+    *out = b;
+    return 0;
+  } catch (std::exception &e) {
+    freeBatchDev(b);
+    delete b;
+    return fail(e.what());
+  }
+}
+
+void readBufInstall(gwa_read_buf_t *out, std::string &&name, std::string &&seq, std::string &&qual,
+                    std::vector<uint64_t> &&nameOff, std::vector<uint64_t> &&seqOff, std::vector<uint64_t> &&qualOff,
+                    std::vector<uint8_t> &&qualNull);  // reads_io.cpp
+
+// gwa_bam_reads_decode and its timed form.  The chain is validated and framed on the host; then the host
+// build decodes record by record, or the kernels decode all of them and the text comes back in one copy.
+// Either way the reads are assembled into compact blobs from (name length, SEQ slot, QUAL slot, no-quality).
+static void bamReadsDecode(int device, const BamSeg &seg, int repeat, gwa_read_buf_t *out, uint64_t *nReads, double *kernelMs) {
+  std::vector<uint64_t> st;
+  (void)bamin::walkChain(seg.bytes, seg.len, true, seg.recIndex, seg.byteOff, &st, nullptr, nullptr);
+  if (st.size() > 0x7FFFFFFFull) throw std::runtime_error("gwa_bam_reads_decode: more than 2^31 - 1 records in one call");
+  const uint32_t n = (uint32_t)st.size();
+  const uint64_t outBytes = bamSlotBytes(seg, st.data(), n);
+  std::vector<uint8_t> text(outBytes + 32), qualNull(n);
+  std::vector<uint64_t> f(6 * (size_t)n + 1);  // nameB nameE seqB seqE qualB qualE
+  if (device < 0) {
+    uint64_t o = 0;
+    for (uint32_t r = 0; r < n; ++r) {
+      const uint8_t *rec = seg.bytes + st[r];
+      const uint64_t l = bamin::fieldsOf(rec).lSeq, slot = bamin::pad16(l);
+      uint32_t nl = 0;
+      bool qn = false;
+      if (bamin::decodeRecord(rec, seg.bytes + seg.len, &nl, &qn, text.data() + o, text.data() + o + slot) != bamin::kOk)
+        throw std::runtime_error(bamRecordError(seg, st[r]));
+      qualNull[r] = qn ? 1 : 0;
+      const uint64_t v[6] = {st[r] + bamin::kFixed, st[r] + bamin::kFixed + nl, o, o + l, o + slot, o + slot + l};
+      for (int k = 0; k < 6; ++k) f[(size_t)k * n + r] = v[k];
+      o += 2 * slot;
+    }
+  } else {
+    HIPCHK(hipSetDevice(device));
+    hipStream_t s = batchStream();
+    BamDecoded d;
+    float ms = 0;
+    const uint64_t segBase[1] = {0};
+    try {
+      bamDecodeDevice(s, &seg, 1, segBase, st.data(), n, seg.len, outBytes, repeat, kernelMs ? &ms : nullptr, &d);
+      if (outBytes) HIPCHK(hipMemcpyAsync(text.data(), d.dOut, outBytes, hipMemcpyDeviceToHost, s));
+      if (n) HIPCHK(hipMemcpyAsync(f.data(), d.fields, 6 * (size_t)n * 8, hipMemcpyDeviceToHost, s));
+      if (n) HIPCHK(hipMemcpyAsync(qualNull.data(), d.qualNull, n, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+    } catch (...) {
+      (void)hipStreamSynchronize(s);
+      bamDecodedFree(&d);
+      batchStreamDone(s);
+      throw;
+    }
+    const uint32_t bad = d.err[0];
+    bamDecodedFree(&d);
+    batchStreamDone(s);
+    if (kernelMs) *kernelMs = ms;
+    if (bad != 0xFFFFFFFFu) {
+      if (bad >= n) throw std::runtime_error("BAM input: the text of the call does not have the size the host computed");
+      throw std::runtime_error(bamRecordError(seg, st[bad]));
+    }
+  }
+  if (nReads) *nReads = n;
+  if (!out) return;
+  std::string name, seq, qual;
+  std::vector<uint64_t> nameOff{0}, seqOff{0}, qualOff{0};
+  for (uint32_t r = 0; r < n; ++r) {
+    const size_t N = n;
+    name.append((const char *)seg.bytes + f[r], f[N + r] - f[r]);
+    seq.append((const char *)text.data() + f[2 * N + r], f[3 * N + r] - f[2 * N + r]);
+    if (!qualNull[r]) qual.append((const char *)text.data() + f[4 * N + r], f[5 * N + r] - f[4 * N + r]);
+    nameOff.push_back(name.size());
+    seqOff.push_back(seq.size());
+    qualOff.push_back(qual.size());
+  }
+  readBufInstall(out, std::move(name), std::move(seq), std::move(qual), std::move(nameOff), std::move(seqOff),
+                 std::move(qualOff), std::move(qualNull));
+}
+
+// pipeline.cpp: the host build over a framed slice (mixed-format pairs)
+int bamDecodeHostSlice(const uint8_t *bytes, uint64_t len, uint64_t recIndex, uint64_t byteOff, const char *label,
+                       gwa_read_buf_t *out) {
+  try {
+    const BamSeg seg{bytes, len, recIndex, byteOff, label};
+    bamReadsDecode(-1, seg, 1, out, nullptr, nullptr);
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
 }  // namespace gwa
 
 extern "C" {
+
+int gwa_bam_reads_decode(int device, const uint8_t *records, uint64_t len, gwa_read_buf_t *out) {
+  try {
+    const BamSeg seg{records, len, 0, 0, nullptr};
+    bamReadsDecode(device, seg, 1, out, nullptr, nullptr);
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+int gwa_bam_reads_decode_timed(int device, const uint8_t *records, uint64_t len, int repeat, uint64_t *n_reads,
+                               double *kernel_ms) {
+  if (device < 0) return fail("gwa_bam_reads_decode_timed: needs a device");
+  try {
+    const BamSeg seg{records, len, 0, 0, nullptr};
+    double ms = 0;
+    bamReadsDecode(device, seg, repeat, nullptr, n_reads, &ms);
+    if (kernel_ms) *kernel_ms = ms;
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+int gwa_bam_header_size(const uint8_t *bam, uint64_t len, uint64_t *header_bytes) {
+  std::string why;
+  const int64_t h = bamin::headerSize(bam, len, &why);
+  if (h == -2) return fail("BAM header: " + why);
+  if (h < 0) return fail("BAM header: the " + std::to_string(len) + " bytes end inside the header");
+  *header_bytes = (uint64_t)h;
+  return 0;
+}
 
 // capacity tiers: (arena, heap, hits, list, cigar, candidates) and the lane budget of each tier
 struct Tier {

@@ -85,6 +85,16 @@ struct Member;
 }
 void launchInflate(const uint8_t *in, uint64_t n, const inflate::Member *ms, uint64_t nMembers, uint8_t *out, uint64_t outCap,
                    uint32_t *status, hipStream_t s);
+// BAM input (bam_in.hip): the records at rec + start[r] (rec 8-byte aligned, 32 bytes of room behind the
+// data) decoded into reads.  Lengths: fields[0..2n) = the names' (B, E) in rec, qualNull, len[r] = the slot
+// of read r in the unpacked text, off = its exclusive scan (n + 1 entries each); err[0] = min(err[0], lowest
+// record with a content error), err[1] += records without a quality.  Unpack: SEQ letters and QUAL characters
+// into out + off[r] (outBytes = off[n]), fields[2n..6n) = their (B, E) in out.
+size_t bamInScanTempBytes(uint32_t n);
+void launchBamInLengths(const uint8_t *rec, const uint64_t *start, uint32_t n, uint64_t *len, uint64_t *off, uint64_t *fields,
+                        uint8_t *qualNull, uint32_t *err, void *scanTmp, size_t scanTmpBytes, hipStream_t s);
+void launchBamInUnpack(const uint8_t *rec, const uint64_t *start, uint32_t n, const uint64_t *off, uint64_t *fields,
+                       const uint8_t *qualNull, uint8_t *out, uint64_t outBytes, uint32_t *err, hipStream_t s);
 size_t sortSearchListTmpBytes(uint32_t n);
 void launchSortSearchList(const uint32_t *listIn, uint32_t *listOut, uint32_t *keysIn, uint32_t *keysOut, uint32_t n,
                           const ScanRes *sres, bool byKey, void *tmp, size_t tmpBytes, hipStream_t s);

@@ -20,6 +20,7 @@
 // batchCreatePairsFastq) and the batch's SAM holds two lines per pair.
 #include <hip/hip_runtime.h>
 
+#include "bam_in_core.h"
 #include "record_stream.h"
 
 #include <algorithm>
@@ -56,6 +57,17 @@ int batchCreatePairsFastq(gwa_index_t *ix, const gwa_config_t *cfg, const char *
                           const uint64_t *start1, const char *text2, uint64_t len2, const uint64_t *start2, uint32_t np,
                           int32_t minInsert, int32_t maxInsert, const char *label1, const char *label2,
                           gwa_batch_t **out);
+// BAM input (gwa_api.cpp): a batch from the framed records of a BAM slice, decoded on the device; the paired
+// form takes two segments, or (bytes2 == nullptr) one interleaved segment whose start1 holds the np mate-1
+// starts and then the np mate-2 starts; and the host build of the decoder over one slice
+int batchCreateBam(gwa_index_t *ix, const gwa_config_t *cfg, const uint8_t *bytes, uint64_t len, const uint64_t *start,
+                   uint32_t n, uint64_t recIndex, uint64_t byteOff, const char *label, gwa_batch_t **out);
+int batchCreatePairsBam(gwa_index_t *ix, const gwa_config_t *cfg, const uint8_t *bytes1, uint64_t len1, const uint64_t *start1,
+                        uint64_t recIndex1, uint64_t byteOff1, const uint8_t *bytes2, uint64_t len2, const uint64_t *start2,
+                        uint64_t recIndex2, uint64_t byteOff2, uint32_t np, int32_t minInsert, int32_t maxInsert,
+                        const char *label1, const char *label2, gwa_batch_t **out);
+int bamDecodeHostSlice(const uint8_t *bytes, uint64_t len, uint64_t recIndex, uint64_t byteOff, const char *label,
+                       gwa_read_buf_t *out);
 // the lowest pair of a paired batch whose mate names differ (false: none)
 bool batchMateNamesDiffer(gwa_batch_t *b, uint32_t *pair, std::string *name1, std::string *name2);
 uint64_t batchSamInto(gwa_batch_t *b, char **buf, uint64_t *cap);  // gwa_api.cpp
@@ -205,6 +217,9 @@ struct Job {
   uint64_t tb2 = 0, te2 = 0;
   int format2 = 1;
   std::vector<uint64_t> starts2;
+  // BAM slices (format 2): where their first record stands in the file (RecordSlice), and the file's name
+  uint64_t recIndex = 0, byteOff = 0, recIndex2 = 0, byteOff2 = 0;
+  std::string label;
 };
 
 // a run's paired-end parameters (gwa_pipeline_align_pair_files / gwa_pipeline_align_pairs)
@@ -524,6 +539,10 @@ struct Run {
         } else if (j.format == 1) {  // FASTQ: the text itself goes to the device, fields located there
           nr = (uint32_t)j.starts.size();
           rc = gwa::batchCreateFastq(ix, &p->cfg, j.text->data() + j.tb, j.te - j.tb, j.starts.data(), nr, &b);
+        } else if (j.format == 2) {  // BAM: the records go to the device and are decoded there
+          nr = (uint32_t)j.starts.size();
+          rc = gwa::batchCreateBam(ix, &p->cfg, (const uint8_t *)j.text->data() + j.tb, j.te - j.tb, j.starts.data(), nr,
+                                   j.recIndex, j.byteOff, j.label.c_str(), &b);
         } else {  // FASTA reads (multi-line records): parsed on the host
           gwa_read_buf_t parsed{};
           uint64_t used = 0;
@@ -583,6 +602,22 @@ struct Run {
     const uint32_t np = (uint32_t)j.pairs;
     const char *t1 = j.text->data() + j.tb;
     const bool inter = !j.text2;
+    if (j.format == 2 && (inter || j.format2 == 2)) {  // BAM mates: decoded on the device
+      const uint8_t *u1 = (const uint8_t *)t1;
+      if (inter) {  // mate-1 starts (even records), then mate-2 starts
+        std::vector<uint64_t> st(2 * (size_t)np);
+        for (uint32_t i = 0; i < np; ++i) {
+          st[i] = j.starts[2 * (size_t)i];
+          st[(size_t)np + i] = j.starts[2 * (size_t)i + 1];
+        }
+        return gwa::batchCreatePairsBam(ix, &p->cfg, u1, j.te - j.tb, st.data(), j.recIndex, j.byteOff, nullptr, 0, nullptr, 0,
+                                        0, np, pair->minInsert, pair->maxInsert, pair->label1.c_str(), nullptr, b);
+      }
+      return gwa::batchCreatePairsBam(ix, &p->cfg, u1, j.te - j.tb, j.starts.data(), j.recIndex, j.byteOff,
+                                      (const uint8_t *)j.text2->data() + j.tb2, j.te2 - j.tb2, j.starts2.data(), j.recIndex2,
+                                      j.byteOff2, np, pair->minInsert, pair->maxInsert, pair->label1.c_str(),
+                                      pair->label2.c_str(), b);
+    }
     if (j.format == 1 && (inter || j.format2 == 1)) {
       if (inter) {  // mate-1 starts (even records), then mate-2 starts
         std::vector<uint64_t> st(2 * (size_t)np);
@@ -600,9 +635,18 @@ struct Run {
     gwa_read_buf_t p1{}, p2{};
     uint64_t used = 0;
     int rc = 0;
+    // (a BAM slice beside a FASTQ or FASTA mate: the host build of the decoder; its messages name the file)
+    auto parse = [&](const char *t, uint64_t len, int fmt, uint64_t recIndex, uint64_t byteOff, const std::string &label,
+                     gwa_read_buf_t *o) {
+      if (fmt == 2) {
+        if (gwa::bamDecodeHostSlice((const uint8_t *)t, len, recIndex, byteOff, label.c_str(), o) != 0)
+          throw std::runtime_error(gwa_last_error());
+      } else if (gwa_reads_parse(t, len, fmt, 1, o, &used) != 0) {
+        throw std::runtime_error(label + ": " + gwa_last_error());
+      }
+    };
     try {
-      if (gwa_reads_parse(t1, j.te - j.tb, j.format, 1, &p1, &used) != 0)
-        throw std::runtime_error(pair->label1 + ": " + gwa_last_error());
+      parse(t1, j.te - j.tb, j.format, j.recIndex, j.byteOff, pair->label1, &p1);
       if (inter) {
         if (p1.reads.n != 2 * np) throw std::runtime_error(pair->label1 + ": the records of a batch do not parse as framed");
         HostReads m1, m2;
@@ -614,8 +658,7 @@ struct Run {
         const gwa_reads_t v1 = m1.view(), v2 = m2.view();
         rc = gwa_batch_create_pairs(ix, &p->cfg, &v1, &v2, pair->minInsert, pair->maxInsert, b);
       } else {
-        if (gwa_reads_parse(j.text2->data() + j.tb2, j.te2 - j.tb2, j.format2, 1, &p2, &used) != 0)
-          throw std::runtime_error(pair->label2 + ": " + gwa_last_error());
+        parse(j.text2->data() + j.tb2, j.te2 - j.tb2, j.format2, j.recIndex2, j.byteOff2, pair->label2, &p2);
         *parsed = Clock::now();
         rc = gwa_batch_create_pairs(ix, &p->cfg, &p1.reads, &p2.reads, pair->minInsert, pair->maxInsert, b);
       }
@@ -1032,6 +1075,9 @@ int gwa_pipeline_align_file_range(gwa_pipeline_t *p, const char *path, int fd, u
       j.te = s.te;
       j.format = s.format;
       j.starts = std::move(s.starts);
+      j.recIndex = s.recIndex;
+      j.byteOff = s.byteOff;
+      if (s.format == 2) j.label = path;
       if (!run.push(std::move(j))) break;
     }
     finishFileRun(p, run, fd, t0, rs.readSeconds(), rs.frameSeconds(), pinnedUsable, {&rs});
@@ -1077,12 +1123,19 @@ int gwa_pipeline_align_pair_files(gwa_pipeline_t *p, const char *path1, const ch
       j.te = s1.te;
       j.format = s1.format;
       j.starts = std::move(s1.starts);
+      j.recIndex = s1.recIndex;
+      j.byteOff = s1.byteOff;
+      // an interleaved BAM: the mate flags, checked here in input order so that the lowest pair is named
+      if (inter && j.format == 2)
+        gwa::bamin::checkMateFlags((const uint8_t *)j.text->data() + j.tb, j.starts.data(), np, (id - 1) * (uint64_t)p->batchReads);
       if (!inter) {
         j.text2 = std::move(s2.buf);
         j.tb2 = s2.tb;
         j.te2 = s2.te;
         j.format2 = s2.format;
         j.starts2 = std::move(s2.starts);
+        j.recIndex2 = s2.recIndex;
+        j.byteOff2 = s2.byteOff;
       }
       if (!run.push(std::move(j))) break;
     }

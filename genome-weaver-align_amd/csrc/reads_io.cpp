@@ -30,6 +30,7 @@ namespace {
 struct Buf {
   std::string name, seq, qual;
   std::vector<uint64_t> nameOff{0}, seqOff{0}, qualOff{0};
+  std::vector<uint8_t> qualNull;  // BAM input: reads without a quality (readBufInstall)
 };
 
 inline bool isWs(unsigned char c) { return c == ' ' || (c >= '\t' && c <= '\r') || (c >= 0x1c && c <= 0x1f); }
@@ -345,6 +346,32 @@ uint64_t frameRecords(const char *t, uint64_t len, int format, bool final, uint6
 }  // namespace gwa
 
 extern "C" int gwa_fail_message(const char *msg);  // gwa_api.cpp: sets gwa_last_error, returns -1
+
+namespace gwa {
+// BAM input (gwa_api.cpp): a read buffer that takes over the decoder's blobs, freed by gwa_reads_free like a
+// parsed one.  Every read has a qual_off range (empty where qualNull marks it as without a quality).
+void readBufInstall(gwa_read_buf_t *out, std::string &&name, std::string &&seq, std::string &&qual,
+                    std::vector<uint64_t> &&nameOff, std::vector<uint64_t> &&seqOff, std::vector<uint64_t> &&qualOff,
+                    std::vector<uint8_t> &&qualNull) {
+  auto *b = new Buf();
+  b->name = std::move(name);
+  b->seq = std::move(seq);
+  b->qual = std::move(qual);
+  b->nameOff = std::move(nameOff);
+  b->seqOff = std::move(seqOff);
+  b->qualOff = std::move(qualOff);
+  b->qualNull = std::move(qualNull);
+  out->priv = b;
+  out->reads.n = (uint32_t)(b->nameOff.size() - 1);
+  out->reads.name = b->name.data();
+  out->reads.seq = b->seq.data();
+  out->reads.qual = b->qual.data();
+  out->reads.name_off = b->nameOff.data();
+  out->reads.seq_off = b->seqOff.data();
+  out->reads.qual_off = b->qualOff.data();
+  out->reads.qual_null = b->qualNull.data();
+}
+}  // namespace gwa
 
 extern "C" int gwa_reads_parse(const char *text, uint64_t len, int format, int final, gwa_read_buf_t *out,
                                uint64_t *consumed) {

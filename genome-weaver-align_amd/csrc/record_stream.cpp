@@ -14,6 +14,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include "bam_in_core.h"
 #include "inflate_host.h"
 #include "snappy_stream.h"
 
@@ -37,6 +38,7 @@ constexpr uint64_t kBgzfRead = 8ull << 20, kBgzfMember = 65536;
 int compressedKind(const char *path) {
   const size_t n = strlen(path);
   if (n > 3 && strcmp(path + n - 3, ".gz") == 0) return 1;
+  if (n > 4 && strcmp(path + n - 4, ".bam") == 0) return 1;
   if (n > 5 && strcmp(path + n - 5, ".snap") == 0) return 2;
   return 0;
 }
@@ -51,6 +53,7 @@ int formatOf(const char *path) {
   };
   if (ends(".fa") || ends(".fasta") || ends(".fan")) return 0;
   if (ends(".fastq") || ends(".fq")) return 1;
+  if (ends(".bam")) return 2;
   throw std::runtime_error(std::string("Unsupported file type: ") + path);
 }
 
@@ -99,6 +102,8 @@ RecordStream::RecordStream(const char *path, uint64_t begin, uint64_t end, uint6
           src_->in = fd;
         } else {
           ::close(fd);
+          if (fmt_ == 2) throw std::runtime_error(std::string(path) + ": not a BAM file: the first BGZF member is missing (" +
+                                                  (why.empty() ? std::string("the file ends inside it") : why) + ")");
         }
       }
     }
@@ -332,6 +337,18 @@ bool RecordStream::frameNextChunk() {
   const uint64_t len = carryLen_ + c.got;
   buf->size = base + len;
   const bool final = c.final;
+  if (fmt == 2) {  // BAM: the header, then the block_size chain
+    const uint64_t pos = frameBam(buf, base, t, len, final);
+    frameS_ += secs(f0, Clock::now());
+    if (final) {
+      ended_ = true;
+    } else {
+      prev_ = buf;
+      carryFrom_ = base + pos;
+      carryLen_ = len - pos;
+    }
+    return true;
+  }
   // all complete records of the text: their header offsets (FASTQ) and the end of the last
   std::vector<uint64_t> &starts = starts_;
   starts.clear();
@@ -420,6 +437,56 @@ bool RecordStream::frameNextChunk() {
     carryLen_ = len - pos;
   }
   return true;
+}
+
+// BAM framing of the text t[0, len) (the carried bytes, then the chunk): the header first, which may take
+// several chunks, then every whole record; slices of batch_ records that are reads.  Returns where the
+// bytes to carry start: the first record that is not in a slice.
+uint64_t RecordStream::frameBam(const std::shared_ptr<TextBuf> &buf, uint64_t base, const char *t, uint64_t len, bool final) {
+  const uint8_t *u = (const uint8_t *)t;
+  uint64_t at = 0;
+  if (!bamHeaderDone_) {
+    std::string why;
+    const int64_t h = bamin::headerSize(u, len, &why);
+    if (h == -2) throw std::runtime_error(path_ + ": " + why);
+    if (h < 0) {
+      if (final) throw std::runtime_error(path_ + ": the BAM header is cut off by the end of the file (" + std::to_string(len) + " bytes)");
+      return 0;  // (all of it carries over)
+    }
+    bamHeaderDone_ = true;
+    at = (uint64_t)h;
+  }
+  std::vector<uint64_t> &starts = starts_;
+  std::vector<uint64_t> idx;
+  starts.clear();
+  uint64_t nAll = 0, done = 0;
+  try {
+    done = at + bamin::walkChain(u + at, len - at, final, bamRec_, bamByte_ + at, &starts, &idx, &nAll);
+  } catch (std::exception &e) {
+    throw std::runtime_error(path_ + ": " + e.what());
+  }
+  for (auto &x : starts) x += at;
+  const uint64_t nrec = starts.size(), B = batch_;
+  const uint64_t full = final ? (nrec + B - 1) / B : nrec / B;
+  for (uint64_t k = 0; k < full; ++k) {
+    const uint64_t r0i = k * B, r1i = std::min(nrec, r0i + B);
+    RecordSlice s;
+    s.buf = buf;
+    s.tb = base + starts[r0i];
+    s.te = base + (r1i < nrec ? starts[r1i] : done);
+    s.n = r1i - r0i;
+    s.format = 2;
+    s.starts.assign(starts.begin() + (long)r0i, starts.begin() + (long)r1i);
+    const uint64_t s0 = starts[r0i];
+    for (auto &x : s.starts) x -= s0;
+    s.recIndex = idx[r0i];
+    s.byteOff = bamByte_ + s0;
+    ready_.push_back(std::move(s));
+  }
+  const uint64_t pos = full * B < nrec ? starts[full * B] : done;
+  bamRec_ = full * B < nrec ? idx[full * B] : bamRec_ + nAll;
+  bamByte_ += pos;
+  return pos;
 }
 
 bool RecordStream::next(RecordSlice *out) {

@@ -37,9 +37,11 @@ struct Member;  // inflate_core.h: a BGZF member's payload and where its text go
 using Inflater = std::function<void(const uint8_t *comp, uint64_t compLen, const inflate::Member *m, uint64_t n,
                                     char *dst, uint64_t dstLen)>;
 
-// 1: gzip (.gz), 2: snappy-java (.snap, R/ReadReaderFactory.java:130-139), 0: plain
+// 1: gzip (.gz, and .bam: a BAM file is a run of BGZF members), 2: snappy-java (.snap,
+// R/ReadReaderFactory.java:130-139), 0: plain
 int compressedKind(const char *path);
-// 0: FASTA (.fa .fasta .fan), 1: FASTQ (.fastq .fq), below an optional .gz / .snap; throws otherwise
+// 0: FASTA (.fa .fasta .fan), 1: FASTQ (.fastq .fq), below an optional .gz / .snap; 2: BAM (.bam); throws
+// otherwise
 int formatOf(const char *path);
 
 // `n` complete records: the bytes [tb, te) of buf.  FASTQ: starts[k] = record k's header line,
@@ -49,6 +51,10 @@ struct RecordSlice {
   uint64_t tb = 0, te = 0, n = 0;
   int format = 1;
   std::vector<uint64_t> starts;
+  // BAM (format 2): [tb, te) is a run of whole alignment records, starts[k] = the k-th of them that is a
+  // read (FLAG without 0x100 and 0x800; the others are skipped); the record at tb is record recIndex of the
+  // file, at byte byteOff of its inflated stream (for error messages)
+  uint64_t recIndex = 0, byteOff = 0;
 };
 
 // A .gz file whose first member is a BGZF member (a gzip member with the BC subfield) is a BGZF source,
@@ -125,6 +131,11 @@ class RecordStream {
   bool ended_ = false;
   std::deque<RecordSlice> ready_;
   std::vector<uint64_t> starts_;
+  // BAM: whether the header has been consumed, and the record index and inflated-stream offset of the
+  // first byte framed next (the carried records' first byte)
+  bool bamHeaderDone_ = false;
+  uint64_t bamRec_ = 0, bamByte_ = 0;
+  uint64_t frameBam(const std::shared_ptr<TextBuf> &buf, uint64_t base, const char *t, uint64_t len, bool final);
 };
 
 // Paired-end input: two record streams, slice k of the one zipped with slice k of the other (the

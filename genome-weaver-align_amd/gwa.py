@@ -128,6 +128,51 @@ def bgzf_decompress_timed(data, device=0, repeat=3):
     return n.value, ms.value
 
 
+def bam_reads_decode(records, device=-1):
+    """The reads of headerless BAM alignment records (include/gwa.h "BAM input", gwa_bam_reads_decode) as
+    [(name, seq, qual-or-None)]: decoded on GPU `device`, or with a negative device by the host build of the
+    same decoder; reads and errors are identical.  Secondary and supplementary records (FLAG 0x100, 0x800)
+    are skipped, FLAG 0x10 records come back reverse-complemented, and qual is None where the record has no
+    quality.  A malformed record raises with its index, byte offset and what was wrong."""
+    import numpy as np
+    records = bytes(records)
+    buf = _ReadBuf()
+    _check(lib().gwa_bam_reads_decode(-1 if device is None else device, records, len(records), ctypes.byref(buf)))
+    try:
+        r = buf.reads
+        n = r.n
+
+        def col(ptr, n):
+            return np.ctypeslib.as_array((ctypes.c_uint64 * (n + 1)).from_address(ptr)).copy() if ptr else None
+        no, so, qo = col(r.name_off, n), col(r.seq_off, n), col(r.qual_off, n)
+        name = ctypes.string_at(r.name, int(no[n])) if n else b""
+        seq = ctypes.string_at(r.seq, int(so[n])) if n else b""
+        qual = ctypes.string_at(r.qual, int(qo[n])) if n and int(qo[n]) else b""
+        qn = ctypes.string_at(r.qual_null, n) if n and r.qual_null else bytes(n)
+        return [(name[int(no[i]):int(no[i + 1])].decode("latin-1"), seq[int(so[i]):int(so[i + 1])].decode("latin-1"),
+                 None if qn[i] else qual[int(qo[i]):int(qo[i + 1])].decode("latin-1")) for i in range(n)]
+    finally:
+        lib().gwa_reads_free(ctypes.byref(buf))
+
+
+def bam_reads_decode_timed(records, device=0, repeat=3):
+    """(reads, milliseconds of the last of `repeat` launches of the length pass, scan and unpack pass over
+    records resident in HBM)"""
+    records = bytes(records)
+    n, ms = ctypes.c_uint64(), ctypes.c_double()
+    _check(lib().gwa_bam_reads_decode_timed(device, records, len(records), repeat, ctypes.byref(n), ctypes.byref(ms)))
+    return n.value, ms.value
+
+
+def bam_header_size(bam):
+    """where the alignment records start in an inflated BAM (gwa_bam_header_size); raises on a wrong magic or
+    an incomplete header"""
+    bam = bytes(bam)
+    n = ctypes.c_uint64()
+    _check(lib().gwa_bam_header_size(bam, len(bam), ctypes.byref(n)))
+    return n.value
+
+
 class PipelineStats(ctypes.Structure):
     _fields_ = [("reads", ctypes.c_uint64), ("batches", ctypes.c_uint64), ("wall_s", ctypes.c_double),
                 ("read_s", ctypes.c_double), ("device_kernel_s", ctypes.c_double * 16), ("parse_s", ctypes.c_double),
@@ -160,6 +205,7 @@ EXPORTS = ["gwa_config_default", "gwa_last_error", "gwa_device_count", "gwa_inde
            "gwa_batch_read_counters", "gwa_batch_results_range", "gwa_results_records", "gwa_batch_results_select", "gwa_batch_format",
            "gwa_batch_sam_copy", "gwa_batch_format_bgzf", "gwa_batch_results_bgzf", "gwa_bgzf_compress", "gwa_bgzf_eof",
            "gwa_bgzf_decompress", "gwa_bgzf_decompress_timed",
+           "gwa_bam_reads_decode", "gwa_bam_reads_decode_timed", "gwa_bam_header_size",
            "gwa_batch_format_bam", "gwa_batch_results_bam_records", "gwa_batch_results_bam", "gwa_bam_header",
            "gwa_bam_header_sorted", "gwa_batch_format_bam_sorted", "gwa_batch_results_bam_sorted", "gwa_batch_bam_sort_times",
            "gwa_bam_sorter_open", "gwa_bam_sorter_add_batch", "gwa_bam_sorter_add_records", "gwa_bam_sorter_finish",
@@ -212,6 +258,9 @@ def lib():
         L.gwa_bgzf_eof.argtypes = [ctypes.c_char_p]
         L.gwa_bgzf_decompress.argtypes = [I, ctypes.c_char_p, U64, P(V), P(U64)]
         L.gwa_bgzf_decompress_timed.argtypes = [I, ctypes.c_char_p, U64, I, P(U64), P(ctypes.c_double)]
+        L.gwa_bam_reads_decode.argtypes = [I, ctypes.c_char_p, U64, P(_ReadBuf)]
+        L.gwa_bam_reads_decode_timed.argtypes = [I, ctypes.c_char_p, U64, I, P(U64), P(ctypes.c_double)]
+        L.gwa_bam_header_size.argtypes = [ctypes.c_char_p, U64, P(U64)]
         L.gwa_batch_format_bam.argtypes = [V, P(U64)]
         L.gwa_batch_results_bam_records.argtypes = [V, P(V), P(U64)]
         L.gwa_batch_results_bam.argtypes = [V, P(V), P(U64)]

@@ -9,6 +9,7 @@ A/AlignmentConfig.java:40-72, A/AlignmentScoreConfig.java:37-77).
   python genome-weaver-align_amd/gwa_cli.py align -r ref.fa mates_1.fq[.gz|.snap] mates_2.fq[.gz|.snap]
          [--insert-min 210] [--insert-max 390] [--check-mate-names]       (paired-end, two SAM lines per pair)
   python genome-weaver-align_amd/gwa_cli.py align -r ref.fa --interleaved pairs.fq   (mates alternating in one file)
+  python genome-weaver-align_amd/gwa_cli.py align -r ref.fa reads.bam | mates_1.bam mates_2.bam | --interleaved pairs.bam
 
 Writes SAM to stdout: the `@SQ` header (SequenceBoundary.toSAMHeader, A/SequenceBoundary.java:81-87)
 then one record per read in input order, as SAMOutput does (A/SAMOutput.java:56-82).  Read files go
@@ -48,6 +49,15 @@ Read input follows ReadReaderFactory.createReader (R/ReadReaderFactory.java:126-
 `.fasta`, `.fan`, `.fastq`, `.fq`, optionally `.gz` or `.snap` (snappy-java stream); `-q` aligns one query named "read" with no
 qualities (R/ReadReaderFactory.java:167-180).  Read names are the first whitespace-delimited token
 of the header line (utgb FastqReader / FASTAPullParser are unvendored: parity unpinned).
+
+A `.bam` file (unaligned or aligned; the reference reads none) is read input too: its BGZF members are inflated
+and its alignment records decoded into reads on the GPU (include/gwa.h "BAM input").  A read is the record's
+name, its SEQ (reverse-complemented back when FLAG has 0x10) and its quality (none when the record has none);
+secondary and supplementary records are skipped; the input's alignment, tags and header are ignored.  The
+output is byte for byte that of the same reads as FASTQ.  `--interleaved pairs.bam` takes mate 1 and mate 2 of
+each pair in turn and checks their flags (0x1 with 0x40, then 0x1 with 0x80), so a coordinate-sorted BAM is
+refused; two `.bam` mate files, or a `.bam` beside a FASTQ file, pair record i with record i.  --shard refuses a
+`.bam` as it refuses a `.gz`.
 """
 import argparse
 import gzip
@@ -75,6 +85,8 @@ def _kind(path):
         return "fasta"
     if p.endswith((".fastq", ".fq")):
         return "fastq"
+    if path.endswith(".bam"):
+        return "bam"
     raise gwa.GwaError("Unsupported file type: " + path)
 
 
@@ -116,6 +128,11 @@ def read_fastq(f):
 
 def reads_of(path):
     kind = _kind(path)  # unsupported suffixes fail before the file is opened
+    if kind == "bam":  # inflated and decoded by the host builds of the library's decoders
+        with open(path, "rb") as fb:
+            data = gwa.bgzf_decompress(fb.read())
+        yield from gwa.bam_reads_decode(data[gwa.bam_header_size(data):], device=-1)
+        return
     f = _open(path)
     try:
         yield from (read_fasta(f) if kind == "fasta" else read_fastq(f))
@@ -129,7 +146,7 @@ def build_parser():
     a = sub.add_parser("align", help="read alignment")
     a.add_argument("-r", dest="refSeq", required=True, help="reference sequence (FASTA)")
     a.add_argument("-q", dest="query", help="single query sequence")
-    a.add_argument("readFiles", nargs="*", help="read file (single-end), or two mate files (paired-end)")
+    a.add_argument("readFiles", nargs="*", help="read file (single-end), or two mate files (paired-end): FASTA, FASTQ (optionally .gz or .snap) or BAM")
     a.add_argument("--silent", action="store_true", help="disable output")
     a.add_argument("-m", dest="strategy", default="bsf", help="alignment strategy: bsf (default), sf, bd, bwa")
     a.add_argument("-R", dest="reportType", default="besthit", help="besthit (default), allhits, topL")

@@ -303,6 +303,45 @@ int gwa_batch_results_bam(gwa_batch_t *b, uint8_t **out, uint64_t *len);
 /* The uncompressed BAM header (gwa_free), built on the host: "BAM\1", l_text and the text gwa_sam_header
  * returns, n_ref, and per contig l_name (with its NUL), the name as RNAME prints it, NUL, l_ref. */
 int gwa_bam_header(const gwa_index_t *ix, uint8_t **out, uint64_t *len);
+/* ---- BAM input: alignment records read as reads, decoded on the device ----
+ * The reference reads no BAM.  A record is the BAMv1 alignment record laid out under "BAM output" above; what
+ * the aligner takes from it is a read:
+ *   name      the read_name bytes before the first NUL, as they are (no whitespace tokenising).  l_read_name 0,
+ *             or no NUL inside l_read_name bytes, is an error.
+ *   sequence  l_seq letters "=ACMGRSVTWYHKDBN"[nibble], the high nibble first.  With FLAG 0x10 the read is the
+ *             reverse complement of the stored SEQ: A<->T, C<->G, M<->K, R<->Y, V<->B, H<->D; S, W, N and '='
+ *             stay.  A letter other than A C G T is treated as that letter is in FASTQ text.
+ *   quality   l_seq > 0 and qual[0] = 0xFF: the read has none (qual_null, QUAL "*"; the other bytes are not
+ *             looked at).  l_seq = 0: the empty string, present, whatever byte follows.  Otherwise byte + 33 per
+ *             base, reversed with FLAG 0x10; a byte above 93 is an error (it would not print as SAM QUAL).
+ *   The input's CIGAR, tags, refID, pos, mapq and mate fields are ignored.  A record with FLAG 0x100 or 0x800
+ *   (secondary, supplementary) is not a read: it is skipped and counts in no read index.
+ * A file is BGZF members whose inflated bytes are "BAM\1", l_text, the text, n_ref, per contig l_name, name and
+ * l_ref, then records to the end.  The header's contigs are ignored (the reference is the index).  Errors: a
+ * wrong magic, a header cut off by the file's end -- both name the file -- and for records "BAM record <index>
+ * at byte <offset in the inflated stream>: <what>", index counting all records, skipped ones too: a block_size
+ * below 32 or below 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq (worded as
+ * gwa_bam_sorter_add_records words it), a record reaching past the data, a chain that ends inside a
+ * block_size field, and the name and quality errors above (the lowest such record).
+ * Equivalence: aligning a BAM file gives, byte for byte, the output of aligning the same reads, in order,
+ * handed over in memory as gwa_reads_t, qual_null set where a record has no quality; where every record has a
+ * quality and l_seq >= 1, that is the output for the equivalent FASTQ file -- SAM, MD, BGZF, BAM, sorted BAM,
+ * single and paired.
+ * On the device: the host walks the block_size chain only; a length pass (one lane per record), a scan and
+ * an unpack pass (16 lanes per record, 16 letters or quality characters per lane and step) produce the read
+ * text in HBM; the names stay in the record bytes (csrc/bam_in.hip).
+ *
+ * Headerless records -> reads (free with gwa_reads_free; every read has a qual_off range, empty where qual_null
+ * marks it).  The chain is validated first.  device >= 0 runs the kernels, device < 0 the host build of the same
+ * decoder (no GPU needed); blobs, offsets, qual_null and errors are identical. */
+int gwa_bam_reads_decode(int device, const uint8_t *records, uint64_t len, gwa_read_buf_t *out);
+/* For timing the kernels alone: the records resident in HBM, length pass + scan + unpack launched `repeat`
+ * times; *kernel_ms = the last round between HIP events, *n_reads = the reads. */
+int gwa_bam_reads_decode_timed(int device, const uint8_t *records, uint64_t len, int repeat, uint64_t *n_reads,
+                               double *kernel_ms);
+/* Where the records start in an inflated BAM (bam[0, len) must hold the whole header).  Negative on a wrong
+ * magic or an incomplete header. */
+int gwa_bam_header_size(const uint8_t *bam, uint64_t len, uint64_t *header_bytes);
 /* ---- Sorted BAM: the records in coordinate order, sorted on the device, and the .bai index ----
  * The reference has nothing here; every part of the rule is a function of the record bytes alone.
  * Order.  A record with refID >= 0 has key = (uint64)(uint32)refID << 32 | ((uint32)pos ^ 0x80000000): the
@@ -428,10 +467,13 @@ int gwa_pipeline_align(gwa_pipeline_t *p, const gwa_reads_t *reads, gwa_results_
  * is inflated on the pipeline's first device, a chunk of whole members per kernel launch (BGZF input
  * above); a later member that is not BGZF, or a truncated last member, fails the run with its byte offset
  * (a missing EOF marker does not).  Any other .gz file is read with zlib on the IO thread.  The SAM is
- * byte for byte the plain file's either way. */
+ * byte for byte the plain file's either way.
+ * A .bam file is read input too ("BAM input" above): it is a BGZF source like a .fastq.gz (GWA_BGZF_INPUT=0:
+ * zlib; a first member that is not BGZF is an error), the reader consumes the header, walks the block_size
+ * chain and cuts batches of records that are reads, and each batch's records are decoded on its device. */
 int gwa_pipeline_align_file(gwa_pipeline_t *p, const char *path, int fd, uint64_t *n_reads);
-/* The same over the bytes [begin, end) of a plain (not .gz / .snap) read file, which must start at a record
- * (gwa_reads_shard_range gives such ranges). */
+/* The same over the bytes [begin, end) of a plain (not .gz / .snap / .bam) read file, which must start at a
+ * record (gwa_reads_shard_range gives such ranges; it refuses a .bam as it refuses a .gz). */
 int gwa_pipeline_align_file_range(gwa_pipeline_t *p, const char *path, int fd, uint64_t begin, uint64_t end,
                                   uint64_t *n_reads);
 /* Paired-end read files streamed through the devices like gwa_pipeline_align_file: mate i of path1
@@ -449,7 +491,13 @@ int gwa_pipeline_align_file_range(gwa_pipeline_t *p, const char *path, int fd, u
  * Errors: -m sf and a bad insert range (as gwa_batch_create_pairs); mate files with different record
  * counts ("the mate files hold different numbers of reads"); an interleaved file with an odd record
  * count; a malformed record (the message starts with the file's name).  What was written to fd before
- * an error is unspecified. */
+ * an error is unspecified.
+ * BAM mates: two .bam files pair record i with record i (records that are reads; no flag check), and both are
+ * decoded on the device in one allocation.  One .bam with path2 == NULL is interleaved: reads 2i and 2i + 1
+ * form pair i, read 2i must carry FLAG 0x1 and 0x40 and read 2i + 1 FLAG 0x1 and 0x80; otherwise the run fails
+ * naming the lowest such pair and both flags (a coordinate-sorted paired BAM fails this way rather than
+ * pairing strangers).  A .bam beside a FASTQ or FASTA mate file is decoded by the host build, as a batch with
+ * a FASTA mate is parsed on the host.  GWA_PAIR_CHECK_NAMES compares the names as they stand in the records. */
 #define GWA_PAIR_CHECK_NAMES 1u
 int gwa_pipeline_align_pair_files(gwa_pipeline_t *p, const char *path1, const char *path2, int32_t min_insert,
                                   int32_t max_insert, uint32_t flags, int fd, uint64_t *n_pairs);
