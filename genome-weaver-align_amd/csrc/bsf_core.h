@@ -877,6 +877,7 @@ struct BsfLane {
   GWA_HD bool isChecked(int s, int ch) { return (S(s).state & (1 << ch)) != 0; }
   GWA_HD void updateFlag(int s, int ch) { S(s).state |= 1 << ch; }
   GWA_HD void updateSplitFlag(int s) { S(s).state |= 1 << 4; }
+  GWA_HD int nextSplitOf(int s) { return s == cacheIdx ? cache.nextSplit : S(s).nextSplit; }
   GWA_HD int numSplit(int s) {
     int n = 0;
     for (int t = S(s).nextSplit; t >= 0; t = S(t).nextSplit) ++n;
@@ -1790,9 +1791,12 @@ struct BsfLane {
 
   // ---- verify (:496-560); returns hit index, -1 = Java null, -2 = overflow ----
   GWA_HD int verify(int s) {
-    const DState<R> d = S(s);
+    // (through the register cache: a deferred head has no arena copy, and a report of the state just
+    // created or polled does not wait on a scratch load)
+    DState<R> d;
+    loadState(s, d);
     const int strand = cStrand(d);
-    if (isClipped(s)) {
+    if ((((uint32_t)d.state >> 25) & 1) != 0) {  // isClipped
       int off = nCigar;
       if (putCigarOp(4, cFrag(d)) < 0) return -2;
       int h = newHit(CHR_NULL, -1, 0, d.start, d.end, 0, strand, off, 1, 0);
@@ -1881,9 +1885,15 @@ struct BsfLane {
 
   // reportAlignment (:562-586); returns false on overflow/error
   GWA_HD bool reportAlignment(int c) {
+    // A deferred head (the cached state, never written back) is chain-free and unreferenced and,
+    // just polled, no longer queued: verify reads it from the cache, and nothing reads it after
+    // this report, so its minK is not stored and it is dropped once the report has succeeded, as
+    // the prune paths drop it (dropIfCached).  Until then it stays cached: a report that is rolled
+    // back runs again from the resume record (laneReport), which holds the cache.
+    const bool deferred = c == cacheIdx && cacheDirty != 0;
     // one verify call site (the DP is large): member 0 is the chain head, the rest hang off it
     int al = -1;
-    for (int nx = c, first = 1; nx >= 0; nx = S(nx).nextSplit, first = 0) {
+    for (int nx = c, first = 1; nx >= 0; nx = nextSplitOf(nx), first = 0) {
       const int res = verify(nx);
       if (res == -2) return false;
       if (first) { al = res; continue; }
@@ -1893,15 +1903,27 @@ struct BsfLane {
     }
     if (al < 0) { status = ST_ERROR; return false; }
     tr(8, (uint32_t)c, (uint32_t)hitTotalMatch(al), (uint32_t)hitTotalDiff(al));
-    if (hitTotalMatch(al) == 0) return true;
     int newK = hitTotalDiff(al);
-    if (newK > k) return true;
-    setMinK(c, newK);
-    refreshKeysFor(c);  // c may still be queued (duplicate references), and chains through it
+    if (hitTotalMatch(al) == 0 || newK > k) {
+      if (deferred) cacheDirty = 0;
+      return true;
+    }
+    if (!deferred) {
+      setMinK(c, newK);
+      refreshKeysFor(c);  // c may still be queued (duplicate references), and chains through it
+    }
+#if !defined(__HIP_DEVICE_COMPILE__)
+    // host builds check the claim above: no queue entry names a deferred head
+    if (deferred)
+      for (int i = 0; i < heapSize; ++i)
+        if ((int)(hslot(i) & IDXM) == c) abort();
+#endif
     int head = sortSplits(al);
     if (status == ST_ERROR || status == ST_OVERFLOW) return false;
     resultAdd(head);
-    return status != ST_OVERFLOW;
+    if (status == ST_OVERFLOW) return false;
+    if (deferred) cacheDirty = 0;
+    return true;
   }
 
   // ---- ReadAlignmentNFA.nextState (S/ReadAlignmentNFA.java:127-203) ----
@@ -2257,7 +2279,8 @@ struct BsfLane {
   enum { LP_RUN = 0, LP_WAIT = 1, LP_FINISH = 2, LP_SUSPEND = 3 };
   int susPhase = LP_RUN;  // the phase a suspended read resumes in (LP_RUN or LP_WAIT: a report pending)
   // room for one micro-step (searchStep), by where it starts: at most 5 new states (a child, then the
-  // split and clip children's 4 when it was the last candidate; or a first child and its run-ahead's
+  // split and clip children's 4 when it was the last candidate or the only one of a text-mode state
+  // (a rejected first child + that tail: 4 states, net 1 queue entry); or a first child and its run-ahead's
   // last state) and, net of a poll (xMode 0), 2 more queue entries; 3 from the next child (1).  0 when
   // there is room, else the OV_* capacity that may run out.
   // (DPM 1, the first tier's kernel: no suspension at all -- its overflows restart on the next tier,
@@ -2396,7 +2419,8 @@ struct BsfLane {
   // clip children come in later calls (xMode 1 / 2), so every lane of a wavefront performs about
   // one FM step per call instead of the wavefront looping until its slowest lane has tried all
   // four bases.  Nothing else touches a lane between its micro-steps, so the order of operations
-  // on its heap and arena is exactly the reference's.
+  // on its heap and arena is exactly the reference's.  (A text-mode state has one non-empty base:
+  // after that child the rest of its expansion has no FM step left and runs in the same call.)
   // (the expanded state xC is re-read from the arena / cache at each micro-step rather than kept
   // in the lane object: its flag word is always stored, so the arena copy is current)
   int xMode = 0, xT = 0, xBase = 0, xC = 0, xNm = 0, xNextBase = 0;
@@ -2430,7 +2454,8 @@ struct BsfLane {
       }
       GWA_PA(PR_POLL, tp);
       if ((((uint32_t)C.state >> 24) & 3) != 0 || cRemaining(C) == 0) {
-        flushCache();  // verify reads the chain from the arena
+        // (a deferred head stays in the cache: verify reads it there; the members of a chain are in
+        // the arena, a poll of anything but the cached state flushed it above)
         pendingBase = base;
         return SS_REPORT;
       }
@@ -2473,8 +2498,13 @@ struct BsfLane {
       xT = tt;
       if (ch >= 0) {
         storeStateWord(xC, xCS.state);
+        // Text mode: ch is the one non-empty base (lb[2]), so what is left of this expansion -- the
+        // other bases, only marked checked, and the split / clip children -- performs no FM step.  It
+        // runs below in this call, on the register copy, instead of in a micro-step of its own that
+        // would first reload xC from the arena; a deferred xC is then dead once ch's child exists.
+        const bool tail = siText(xCS);
         GWA_PT(tn);
-        int ns = nextStateLocal(xC, xCS, ch, first && xC == xBase && deferrable(xCS));
+        int ns = nextStateLocal(xC, xCS, ch, (first || tail) && xC == xBase && deferrable(xCS));
         GWA_PA(PR_LOOP, tn);
         if (ns == -2) return SS_DONE;
         if (ns >= 0) {
@@ -2494,7 +2524,15 @@ struct BsfLane {
           }
         }
         GWA_PA(PR_EXPN, te);
-        if (xT < 4) return SS_CONTINUE;  // more candidates: next call
+        if (xT < 4) {
+          if (!tail) return SS_CONTINUE;  // more candidates: next call
+          // what the next call's loop would do from xT on: every base left is checked or empty, and
+          // the staircase check of :439 is due if the loop over every base begins here (xT == 0: ch
+          // was nextBase)
+          if (xT == 0 && !stairOk()) return SS_DONE;
+          xCS.state |= (0xF << xT) & 0xF;
+          xT = 4;
+        }
       }
       xMode = 2;
     }
@@ -2527,9 +2565,11 @@ struct BsfLane {
   // Write-back deferral: a new state that no split chain holds (nextSplit < 0, no kStRef) stays
   // only in the cache (cacheDirty) until it is evicted.  The usual next poll returns it, and when
   // its own next base is accepted the reference drops it (:386-396: the child is pushed, the parent
-  // is not) -- its arena copy would never be read, so it is never written.  Every other path writes
-  // it back first (flushCache): a poll of another state, a report, a chain operation, an eviction
-  // by a state other than its accepted first child.
+  // is not) -- its arena copy would never be read, so it is never written.  The same holds when it
+  // is reported (reportAlignment: verified from the cache, dead after the report) and when its one
+  // text-mode child is taken and its split / clip children follow in the same call (searchStep).
+  // Every other path writes it back first (flushCache): a poll of another state, a chain operation,
+  // an eviction by any other child.
   int cacheIdx = -1, cacheDirty = 0;
   DState<R> cache;
   GWA_HD void flushCache() {

@@ -54,7 +54,10 @@ def _timed_ids(d, sub, win):
     ids = set()
     if win is None:
         return None
-    for r in _rows(os.path.join(d, sub, "**", "*_kernel_trace.csv")):
+    rows = _rows(os.path.join(d, sub, "**", "*_kernel_trace.csv"))
+    if not rows:  # a counter pass taken without a kernel trace: every dispatch of the pass counts
+        return None
+    for r in rows:
         if _short(r["Kernel_Name"]) and int(r["Start_Timestamp"]) >= win[0] and int(r["End_Timestamp"]) <= win[1]:
             ids.add(r["Dispatch_Id"])
     return ids
