@@ -14,6 +14,8 @@
 //      (destination, source) offsets in LDS, and every lane builds aligned 16-byte output pieces from
 //      unaligned 16-byte loads of the one or two records a piece spans.  Every output byte is written by
 //      exactly one lane from exactly one source byte: nothing depends on a race.
+//   7. only with duplicate marking (wantDup): the records' entries in input order and their permuted,
+//      completed form (bam_dup.hip).  Without it nothing here is launched or allocated.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -23,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "bam_dup.h"
 #include "bam_sort.h"
 
 namespace gwa {
@@ -186,7 +189,7 @@ void grow(T **p, size_t *cap, size_t need) {
   *cap = want;
 }
 struct Ev {
-  hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   Ev() {
     for (auto &x : e) SCHK(hipEventCreate(&x));
   }
@@ -201,6 +204,8 @@ struct BamSortBuf {
   uint64_t *cnt = nullptr, *first = nullptr, *srcOff = nullptr, *keys = nullptr, *keysOut = nullptr, *psize = nullptr, *dstOff = nullptr;
   uint32_t *ord = nullptr, *perm = nullptr;
   BamRecInfo *info = nullptr, *infoSorted = nullptr;
+  bamdup::BamDupInfo *dupStage = nullptr, *dupSorted = nullptr;  // only with duplicate marking
+  size_t dupStageCap = 0, dupSortedCap = 0;
   uint8_t *tmp = nullptr, *sorted = nullptr;
   size_t cntCap = 0, firstCap = 0, srcOffCap = 0, keysCap = 0, keysOutCap = 0, psizeCap = 0, dstOffCap = 0, ordCap = 0, permCap = 0,
          infoCap = 0, infoSortedCap = 0, tmpCap = 0, sortedCap = 0;
@@ -210,7 +215,7 @@ BamSortBuf *bamSortCreate() { return new BamSortBuf(); }
 void bamSortFree(BamSortBuf *b) {
   if (!b) return;
   void *ps[] = {b->cnt, b->first, b->srcOff, b->keys, b->keysOut, b->psize, b->dstOff, b->ord, b->perm, b->info, b->infoSorted, b->tmp,
-                b->sorted};
+                b->sorted, b->dupStage, b->dupSorted};
   for (void *p : ps)
     if (p) (void)hipFree(p);
   delete b;
@@ -219,7 +224,7 @@ void bamSortFree(BamSortBuf *b) {
 static inline dim3 gridFor(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
 
 void bamSortRun(BamSortBuf *b, const uint8_t *d_text, uint64_t bytes, uint64_t textCap, const uint64_t *d_off, uint64_t n,
-                void *stream, BamSortResult *out) {
+                void *stream, BamSortResult *out, bool wantDup) {
   hipStream_t s = (hipStream_t)stream;
   *out = BamSortResult{};
   if (n == 0 || bytes == 0) return;
@@ -274,6 +279,16 @@ void bamSortRun(BamSortBuf *b, const uint8_t *d_text, uint64_t bytes, uint64_t t
                      b->perm, b->dstOff, R, total, b->sorted);
   SCHK(hipGetLastError());
   SCHK(hipEventRecord(ev.e[3], s));
+  if (wantDup) {  // the records' duplicate-marking entries, in sorted order (bam_dup.hip)
+    grow(&b->dupStage, &b->dupStageCap, R);
+    grow(&b->dupSorted, &b->dupSortedCap, R);
+    bamDupLaunch(d_text, b->srcOff, b->info, R, b->dupStage, s);
+    bamDupPermuteLaunch(b->dupStage, b->perm, R, b->dupSorted, s);
+    SCHK(hipEventRecord(ev.e[5], s));
+    SCHK(hipEventSynchronize(ev.e[5]));
+    SCHK(hipEventElapsedTime(&out->dup_ms, ev.e[3], ev.e[5]));
+    out->d_dup = b->dupSorted;
+  }
   SCHK(hipEventSynchronize(ev.e[3]));
   SCHK(hipEventElapsedTime(&out->walk_ms, ev.e[0], ev.e[1]));
   SCHK(hipEventElapsedTime(&out->sort_ms, ev.e[1], ev.e[2]));
@@ -286,7 +301,8 @@ void bamSortRun(BamSortBuf *b, const uint8_t *d_text, uint64_t bytes, uint64_t t
   out->bytes = total;
 }
 
-void bamSortBytesDevice(int device, const uint8_t *bytes, const uint64_t *off, uint64_t n, uint8_t *sorted, BamRecInfo *info) {
+void bamSortBytesDevice(int device, const uint8_t *bytes, const uint64_t *off, uint64_t n, uint8_t *sorted, BamRecInfo *info,
+                        bamdup::BamDupInfo *dup, double *dupSeconds) {
   if (n == 0) return;
   SCHK(hipSetDevice(device));
   const uint64_t len = off[n];
@@ -309,10 +325,14 @@ void bamSortBytesDevice(int device, const uint8_t *bytes, const uint64_t *off, u
     SCHK(hipMemcpyAsync(dOff, off, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     b = bamSortCreate();
     BamSortResult r;
-    bamSortRun(b, dText, len, len, dOff, n, s, &r);
+    bamSortRun(b, dText, len, len, dOff, n, s, &r, dup != nullptr);
     if (r.records != n) throw std::runtime_error("bam_sort: the device counted " + std::to_string(r.records) + " of " + std::to_string(n) + " records");
     SCHK(hipMemcpyAsync(sorted, r.d_sorted, len, hipMemcpyDeviceToHost, s));
     SCHK(hipMemcpyAsync(info, r.d_info, n * sizeof(BamRecInfo), hipMemcpyDeviceToHost, s));
+    if (dup) {
+      SCHK(hipMemcpyAsync(dup, r.d_dup, n * sizeof(bamdup::BamDupInfo), hipMemcpyDeviceToHost, s));
+      if (dupSeconds) *dupSeconds += r.dup_ms * 1e-3;
+    }
     SCHK(hipStreamSynchronize(s));
   } catch (...) {
     release();

@@ -118,8 +118,9 @@ inline std::vector<uint64_t> validateChain(const uint8_t *bytes, uint64_t len) {
 }
 
 // The host build of the batch sort: the records of bytes (record offsets off[0 .. n]) stably sorted by key.
+// permOut (may be null): the input ordinal of every sorted record.
 inline void sortHost(const uint8_t *bytes, const uint64_t *off, uint64_t n, std::vector<uint8_t> &sorted,
-                     std::vector<BamRecInfo> &info) {
+                     std::vector<BamRecInfo> &info, std::vector<uint64_t> *permOut = nullptr) {
   std::vector<BamRecInfo> in(n);
   for (uint64_t i = 0; i < n; ++i) in[i] = infoOf(bytes + off[i], (uint32_t)(off[i + 1] - off[i]));
   std::vector<uint64_t> perm(n);
@@ -133,6 +134,7 @@ inline void sortHost(const uint8_t *bytes, const uint64_t *off, uint64_t n, std:
     memcpy(sorted.data() + at, bytes + off[perm[i]], info[i].size);
     at += info[i].size;
   }
+  if (permOut) permOut->swap(perm);
 }
 
 // The uncompressed header of a sorted file from the plain one (bamHeader's bytes: "BAM\1", l_text, the text,

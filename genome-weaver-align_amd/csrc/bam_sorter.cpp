@@ -17,12 +17,14 @@
 #include "bgzf_host.h"
 #else
 #include "../../include/gwa.h"
+#include "bam_dup.h"
 #include "bam_sort.h"
 #endif
 
 namespace gwa {
 
 using namespace bamsort;
+using bamdup::BamDupInfo;
 
 namespace {
 double now() {
@@ -83,25 +85,70 @@ void BamSorter::addRecords(uint64_t runId, const uint8_t *bytes, uint64_t len) {
   const uint64_t n = off.size() - 1;
   std::vector<uint8_t> sorted;
   std::vector<BamRecInfo> info;
+  std::vector<BamDupInfo> dup;
+  const bool md = markdup_;
+  double dupS = 0;
 #ifndef GWA_BAM_SORT_HOST_ONLY
   if (device_ >= 0) {
     sorted.resize(len);
     info.resize(n);
-    bamSortBytesDevice(device_, bytes, off.data(), n, sorted.data(), info.data());
+    if (md) dup.resize(n);
+    bamSortBytesDevice(device_, bytes, off.data(), n, sorted.data(), info.data(), md ? dup.data() : nullptr, &dupS);
   } else
 #endif
-    sortHost(bytes, off.data(), n, sorted, info);
-  addSortedRun(runId, std::move(sorted), std::move(info));
+  {
+    std::vector<uint64_t> perm;
+    sortHost(bytes, off.data(), n, sorted, info, md ? &perm : nullptr);
+    if (md) {
+      const double t0 = now();
+      std::vector<BamDupInfo> in;
+      bamdup::runHost(bytes, off.data(), n, in);
+      dup.resize(n);
+      for (uint64_t i = 0; i < n; ++i) dup[i] = in[perm[i]];
+      dupS = now() - t0;
+    }
+  }
+  if (md) {
+    addDupSeconds(dupS);
+    addSortedRun(runId, std::move(sorted), std::move(info), std::move(dup));
+  } else {
+    addSortedRun(runId, std::move(sorted), std::move(info));
+  }
+}
+
+void BamSorter::setMarkdup(bool on) {
+  std::lock_guard<std::mutex> g(mu_);
+  if (added_) throw std::runtime_error("gwa_bam_sorter_set_markdup: duplicate marking is set before the first run is added");
+  markdup_ = on;
 }
 
 void BamSorter::addSortedRun(uint64_t runId, std::vector<uint8_t> &&sorted, std::vector<BamRecInfo> &&info) {
+  addSortedRun(runId, std::move(sorted), std::move(info), std::vector<BamDupInfo>());
+}
+
+void BamSorter::addSortedRun(uint64_t runId, std::vector<uint8_t> &&sorted, std::vector<BamRecInfo> &&info,
+                             std::vector<BamDupInfo> &&dup) {
   const double t0 = now();
   Run run;
   run.len = sorted.size();
   run.info = std::move(info);
+  if (markdup_) {  // the run's templates: its distinct leaders (every one a record of the run)
+    const uint64_t n = run.info.size();
+    if (dup.size() != n)
+      throw std::runtime_error("gwa_bam_sorter: run " + std::to_string(runId) + " has " + std::to_string(n) + " records and " +
+                               std::to_string(dup.size()) + " duplicate-marking entries");
+    std::vector<uint8_t> seen(n, 0);
+    for (const BamDupInfo &x : dup) {
+      if (x.leader >= n) throw std::runtime_error("gwa_bam_sorter: run " + std::to_string(runId) + " names a template leader outside the run");
+      run.templates += !seen[x.leader];
+      seen[x.leader] = 1;
+    }
+    run.dup = std::move(dup);
+  }
   bool spill = false;
   {
     std::lock_guard<std::mutex> g(mu_);
+    added_ = true;
     if (runs_.count(runId)) throw std::runtime_error("gwa_bam_sorter: run " + std::to_string(runId) + " was added twice");
     if (run.len && (memUsed_ + run.len > memBytes_ || memUsed_ + run.len < memUsed_)) {
       if (!haveTmp_)
@@ -160,6 +207,7 @@ void BamSorter::finish(int fdBam, int fdBai, BamSorterStats *stOut) {
     uint64_t next = 0, off = 0;
   };
   std::vector<Cursor> cur;
+  bamdup::DupStats ds;
   auto closeAll = [&]() {
     for (auto &c : cur)
       if (c.f) fclose(c.f);
@@ -202,6 +250,30 @@ void BamSorter::finish(int fdBam, int fdBai, BamSorterStats *stOut) {
         orderHost(keys.data(), N, perm.data());
     }
     st_.order_s += now() - t;
+    // the duplicate templates: one bit per global template ordinal (run-major input ordinal of the leader)
+    std::vector<uint32_t> dupBits;
+    if (markdup_) {
+      t = now();
+      std::vector<BamDupInfo> all(N);
+      uint64_t at = 0;
+      size_t k = 0;
+      for (auto &r : runs_) {
+        for (BamDupInfo x : r.second.dup) {
+          x.leader = (uint32_t)(runStart[k] + x.leader);
+          all[at++] = x;
+        }
+        ds.templates += r.second.templates;
+        ++k;
+      }
+      dupBits.assign((size_t)((N + 31) / 32), 0u);
+#ifndef GWA_BAM_SORT_HOST_ONLY
+      if (device_ >= 0) bamDupResolveDevice(device_, all.data(), N, N, dupBits.data(), &ds);
+      else
+#endif
+        bamdup::resolveHost(all.data(), N, N, dupBits, &ds);
+      ds.resolve_s = now() - t;
+      ds.keys_s = dupKeysS_;
+    }
     // 2.-5. the copy into parts of whole slices, each compressed and written
     const uint64_t partBytes = (uint64_t)partSlices_ * kSlice;
     std::vector<uint8_t> part(N ? partBytes : 0), blocks, rec;
@@ -235,7 +307,7 @@ void BamSorter::finish(int fdBam, int fdBai, BamSorterStats *stOut) {
       if (gidx - runStart[k] != c.next) throw std::runtime_error("gwa_bam_sorter: a run is not in key order");
       const uint32_t size = run.info[c.next].size;
       if (c.off + size > run.len) throw std::runtime_error("gwa_bam_sorter: a run is shorter than its records");
-      const uint8_t *src;
+      uint8_t *src;
       if (run.path.empty()) {
         src = run.bytes.data() + c.off;
       } else {
@@ -246,6 +318,14 @@ void BamSorter::finish(int fdBam, int fdBai, BamSorterStats *stOut) {
         rec.resize(size);
         if (fread(rec.data(), 1, size, c.f) != size) throw std::runtime_error("gwa_bam_sorter: reading back " + run.path + " failed");
         src = rec.data();
+      }
+      if (markdup_) {  // (before the copy: a record straddling two parts needs no special case)
+        const BamDupInfo &d = run.dup[c.next];
+        const uint64_t o = runStart[k] + d.leader;
+        if (d.endKey != bamdup::kNoKey && (dupBits[o >> 5] >> (o & 31) & 1u)) {
+          src[bamdup::kFlagByte] |= (uint8_t)(bamdup::kDupFlag >> 8);
+          ++ds.dup_records;
+        }
       }
       uint32_t done = 0;
       while (done < size) {
@@ -293,12 +373,17 @@ void BamSorter::finish(int fdBam, int fdBai, BamSorterStats *stOut) {
   } catch (...) {
     closeAll();
     dropRuns();
+    added_ = false;
+    dupKeysS_ = 0;
     throw;
   }
   closeAll();
   dropRuns();
   if (stOut) *stOut = st_;
   st_ = BamSorterStats{};
+  lastDup_ = ds;
+  added_ = false;
+  dupKeysS_ = 0;
 }
 
 }  // namespace gwa

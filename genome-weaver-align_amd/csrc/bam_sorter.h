@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "bam_dup_core.h"
 #include "bam_sort_core.h"
 
 namespace gwa {
@@ -30,6 +31,20 @@ class BamSorter {
   void addRecords(uint64_t runId, const uint8_t *bytes, uint64_t len);
   // a batch's sorted records and their per-record array
   void addSortedRun(uint64_t runId, std::vector<uint8_t> &&sorted, std::vector<bamsort::BamRecInfo> &&info);
+  // the same with the records' duplicate-marking entries, in the same order (needed when marking is on)
+  void addSortedRun(uint64_t runId, std::vector<uint8_t> &&sorted, std::vector<bamsort::BamRecInfo> &&info,
+                    std::vector<bamdup::BamDupInfo> &&dup);
+  // Duplicate marking (include/gwa.h "Duplicate marking") for the runs added from now on; refused once a run
+  // of the current scope has been added.
+  void setMarkdup(bool on);
+  bool markdup() const { return markdup_; }
+  // counts and times of the last finish with marking on (zero otherwise)
+  bamdup::DupStats markdupStats() const { return lastDup_; }
+  // seconds of a run's per-run duplicate pass made before addSortedRun: counted as keys_s
+  void addDupSeconds(double s) {
+    std::lock_guard<std::mutex> g(mu_);
+    dupKeysS_ += s;
+  }
   // the sorted stream as BGZF blocks to fdBam, the index to fdBai (-1: none); the runs are consumed
   void finish(int fdBam, int fdBai, BamSorterStats *st);
   // seconds spent on a run before addSortedRun (a batch's device sort and its copy to the host): counted as add_s
@@ -44,6 +59,8 @@ class BamSorter {
   struct Run {
     std::vector<uint8_t> bytes;  // empty when spilled
     std::vector<bamsort::BamRecInfo> info;
+    std::vector<bamdup::BamDupInfo> dup;  // in the same order; only with duplicate marking
+    uint64_t templates = 0;
     std::string path;            // the spill file
     uint64_t len = 0;
   };
@@ -58,6 +75,9 @@ class BamSorter {
   std::mutex mu_;
   std::map<uint64_t, Run> runs_;
   BamSorterStats st_;
+  bool markdup_ = false, added_ = false;
+  double dupKeysS_ = 0;
+  bamdup::DupStats lastDup_;
 };
 
 }  // namespace gwa

@@ -21,6 +21,7 @@
 
 #include "bam_core.h"
 #include "bam_in_core.h"
+#include "bam_dup.h"
 #include "bam_sort.h"
 #include "bam_sorter.h"
 #include "bgzf_host.h"
@@ -2413,13 +2414,13 @@ int gwa_bam_header(const gwa_index_t *ix, uint8_t **out, uint64_t *len) {
 }
 
 // the whole batch's BAM records formatted (bamOnDevice) and put into coordinate order in HBM (bam_sort.hip)
-static void bamSortedOnDevice(gwa_batch_t *b, BamSortResult *r) {
+static void bamSortedOnDevice(gwa_batch_t *b, BamSortResult *r, bool wantDup = false) {
   const uint64_t total = bamOnDevice(b);
   b->sortTimes = gwa_bam_sort_times_t{};
   *r = BamSortResult{};
   if (!total) return;
   if (!b->sortBuf) b->sortBuf = bamSortCreate();
-  bamSortRun(b->sortBuf, (const uint8_t *)b->d_fmtText, total, total, b->d_fmtOff, b->pairs ? b->pairs : b->n, b->stream, r);
+  bamSortRun(b->sortBuf, (const uint8_t *)b->d_fmtText, total, total, b->d_fmtOff, b->pairs ? b->pairs : b->n, b->stream, r, wantDup);
   b->sortTimes.walk_ms = r->walk_ms;
   b->sortTimes.sort_ms = r->sort_ms;
   b->sortTimes.permute_ms = r->permute_ms;
@@ -2455,6 +2456,58 @@ int gwa_batch_results_bam_sorted(gwa_batch_t *b, uint8_t **records, uint64_t *le
   } catch (std::exception &e) {
     free(rec);
     free(k);
+    return fail(e.what());
+  }
+}
+
+int gwa_batch_results_bam_dupinfo(gwa_batch_t *b, uint8_t **info, uint64_t *n_records) {
+  uint8_t *d = nullptr;
+  try {
+    BamSortResult r;
+    bamSortedOnDevice(b, &r, true);
+    uint64_t dl = 0;
+    copyOut(b, r.d_dup, r.records * sizeof(bamdup::BamDupInfo), "the duplicate-marking entries", &d, &dl);
+    *info = d;
+    *n_records = r.records;
+    return 0;
+  } catch (std::exception &e) {
+    free(d);
+    return fail(e.what());
+  }
+}
+
+int gwa_bam_records_dupinfo(int device, const uint8_t *records, uint64_t len, uint8_t **info, uint64_t *n_records) {
+  try {
+    const std::vector<uint64_t> off = bamsort::validateChain(records, len);
+    const uint64_t n = off.size() - 1;
+    std::vector<bamdup::BamDupInfo> d;
+    if (device >= 0) {
+      d.resize(n);
+      bamDupRunTimed(device, records, off.data(), n, 1, d.data(), nullptr);
+    } else {
+      bamdup::runHost(records, off.data(), n, d);
+    }
+    uint8_t *p = (uint8_t *)malloc(n * sizeof(bamdup::BamDupInfo) + 1);
+    if (!p) throw std::runtime_error("out of host memory for the duplicate-marking entries");
+    memcpy(p, d.data(), n * sizeof(bamdup::BamDupInfo));
+    *info = p;
+    *n_records = n;
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+int gwa_bam_markdup_timed(int device, const uint8_t *records, uint64_t len, int repeat, uint64_t *n, double *kernel_ms) {
+  if (device < 0) return fail("gwa_bam_markdup_timed: needs a device");
+  try {
+    const std::vector<uint64_t> off = bamsort::validateChain(records, len);
+    double ms = 0;
+    bamDupRunTimed(device, records, off.data(), off.size() - 1, repeat, nullptr, &ms);
+    if (n) *n = off.size() - 1;
+    if (kernel_ms) *kernel_ms = ms;
+    return 0;
+  } catch (std::exception &e) {
     return fail(e.what());
   }
 }
@@ -2496,17 +2549,25 @@ int gwa_bam_sorter_open(const gwa_index_t *ix, int device, const char *tmp_dir, 
 int gwa_bam_sorter_add_batch(gwa_bam_sorter_t *s, uint64_t run_id, gwa_batch_t *b) {
   try {
     const auto t0 = std::chrono::steady_clock::now();
+    const bool md = s->s.markdup();
     BamSortResult r;
-    bamSortedOnDevice(b, &r);
+    bamSortedOnDevice(b, &r, md);
     std::vector<uint8_t> bytes(r.bytes);
     std::vector<bamsort::BamRecInfo> info(r.records);
+    std::vector<bamdup::BamDupInfo> dup(md ? r.records : 0);
     if (r.records) {
+      if (md) HIPCHK(hipMemcpyAsync(dup.data(), r.d_dup, r.records * sizeof(bamdup::BamDupInfo), hipMemcpyDeviceToHost, b->stream));
       HIPCHK(hipMemcpyAsync(bytes.data(), r.d_sorted, r.bytes, hipMemcpyDeviceToHost, b->stream));
       HIPCHK(hipMemcpyAsync(info.data(), r.d_info, r.records * sizeof(bamsort::BamRecInfo), hipMemcpyDeviceToHost, b->stream));
       HIPCHK(hipStreamSynchronize(b->stream));
     }
     s->s.addSeconds(std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-    s->s.addSortedRun(run_id, std::move(bytes), std::move(info));
+    if (md) {
+      s->s.addDupSeconds(r.dup_ms * 1e-3);
+      s->s.addSortedRun(run_id, std::move(bytes), std::move(info), std::move(dup));
+    } else {
+      s->s.addSortedRun(run_id, std::move(bytes), std::move(info));
+    }
     return 0;
   } catch (std::exception &e) {
     return fail(e.what());
@@ -2546,6 +2607,28 @@ int gwa_bam_sorter_finish(gwa_bam_sorter_t *s, int fd_bam, int fd_bai, gwa_bam_s
   } catch (std::exception &e) {
     return fail(e.what());
   }
+}
+
+int gwa_bam_sorter_set_markdup(gwa_bam_sorter_t *s, int on) {
+  try {
+    s->s.setMarkdup(on != 0);
+    return 0;
+  } catch (std::exception &e) {
+    return fail(e.what());
+  }
+}
+
+int gwa_bam_sorter_markdup_stats(const gwa_bam_sorter_t *s, gwa_markdup_stats_t *st) {
+  const bamdup::DupStats x = s->s.markdupStats();
+  st->templates = x.templates;
+  st->pair_templates = x.pair_templates;
+  st->frag_templates = x.frag_templates;
+  st->dup_pair_templates = x.dup_pair_templates;
+  st->dup_frag_templates = x.dup_frag_templates;
+  st->dup_records = x.dup_records;
+  st->keys_s = x.keys_s;
+  st->resolve_s = x.resolve_s;
+  return 0;
 }
 
 void gwa_bam_sorter_close(gwa_bam_sorter_t *s) { delete s; }

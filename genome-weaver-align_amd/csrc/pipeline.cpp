@@ -294,6 +294,8 @@ struct gwa_pipeline {
   uint64_t sortMem = 0;
   int sortBaiFd = -1;
   gwa_bam_sorter_stats_t sortStats{};  // of the last sorted call
+  bool markdupOn = false;                // duplicate marking in the sort scope (gwa_pipeline_set_markdup)
+  gwa_markdup_stats_t markdupStats{};    // of the last sorted call
   BufPool pool;  // pinned read-text buffers, kept across align_file calls
   uint64_t pinnedBufs = 0, pinnedBytes = 0;  // pinned so far (lazily, by align_file)
   std::mutex samMu;
@@ -802,6 +804,18 @@ int gwa_pipeline_set_sort(gwa_pipeline_t *p, const char *tmp_dir, uint64_t mem_b
   return 0;
 }
 
+int gwa_pipeline_set_markdup(gwa_pipeline_t *p, int on) {
+  if (!p->sortOn)
+    return gwa_fail_message("gwa_pipeline_set_markdup: duplicate marking needs a pipeline that sorts (gwa_pipeline_set_sort)");
+  p->markdupOn = on != 0;
+  return 0;
+}
+
+int gwa_pipeline_markdup_stats(const gwa_pipeline_t *p, gwa_markdup_stats_t *st) {
+  *st = p->markdupStats;
+  return 0;
+}
+
 int gwa_pipeline_sort_stats(const gwa_pipeline_t *p, gwa_bam_sorter_stats_t *st) {
   *st = p->sortStats;
   return 0;
@@ -978,6 +992,7 @@ void setOutput(Run &run, int fd) {
     if (gwa_bam_sorter_open(p->ix[0], gwa::indexDevice(p->ix[0]), p->sortHasTmp ? p->sortTmp.c_str() : nullptr, p->sortMem,
                             &run.sort.s) != 0)
       throw std::runtime_error(gwa_last_error());
+    if (p->markdupOn && gwa_bam_sorter_set_markdup(run.sort.s, 1) != 0) throw std::runtime_error(gwa_last_error());
   }
 }
 
@@ -1026,6 +1041,8 @@ void finishFileRun(gwa_pipeline *p, Run &run, int fd, Clock::time_point t0, doub
     p->sortStats = gwa_bam_sorter_stats_t{};
     if (gwa_bam_sorter_finish(run.sort.s, fd, p->sortBaiFd, &p->sortStats) != 0) throw std::runtime_error(gwa_last_error());
     run.outBytes += p->sortStats.out_bytes;
+    p->markdupStats = gwa_markdup_stats_t{};
+    (void)gwa_bam_sorter_markdup_stats(run.sort.s, &p->markdupStats);
   }
   gwa_pipeline_stats_t &st = p->stats;
   st = gwa_pipeline_stats_t{};

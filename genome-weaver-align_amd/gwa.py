@@ -164,6 +164,28 @@ def bam_reads_decode_timed(records, device=0, repeat=3):
     return n.value, ms.value
 
 
+def bam_records_dupinfo(records, device=0):
+    """[(endKey, mateKey, score, leader)] of unsorted records, in input order (gwa_bam_records_dupinfo: the
+    per-run duplicate-marking pass on the device, device < 0: its host build)"""
+    import struct
+    records = bytes(records)
+    out, n = ctypes.c_void_p(), ctypes.c_uint64()
+    _check(lib().gwa_bam_records_dupinfo(device, records, len(records), ctypes.byref(out), ctypes.byref(n)))
+    try:
+        return list(struct.iter_unpack("<QQII", ctypes.string_at(out, 24 * n.value)))
+    finally:
+        lib().gwa_free(out)
+
+
+def bam_markdup_timed(records, device=0, repeat=3):
+    """(records, milliseconds of the last of `repeat` launches of the per-run duplicate-marking kernel over
+    records resident in HBM)"""
+    records = bytes(records)
+    n, ms = ctypes.c_uint64(), ctypes.c_double()
+    _check(lib().gwa_bam_markdup_timed(device, records, len(records), repeat, ctypes.byref(n), ctypes.byref(ms)))
+    return n.value, ms.value
+
+
 def bam_header_size(bam):
     """where the alignment records start in an inflated BAM (gwa_bam_header_size); raises on a wrong magic or
     an incomplete header"""
@@ -195,6 +217,19 @@ class BamSorterStats(ctypes.Structure):
                [(n, ctypes.c_double) for n in ("add_s", "order_s", "copy_s", "compress_s", "write_s", "index_s")]
 
 
+class MarkdupStats(ctypes.Structure):
+    """gwa_markdup_stats_t"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("templates", "pair_templates", "frag_templates", "dup_pair_templates",
+                                               "dup_frag_templates", "dup_records")] + \
+               [(n, ctypes.c_double) for n in ("keys_s", "resolve_s")]
+
+
+class BamDupInfo(ctypes.Structure):
+    """the 24-byte entry of gwa_batch_results_bam_dupinfo (csrc/bam_dup_core.h)"""
+    _fields_ = [("endKey", ctypes.c_uint64), ("mateKey", ctypes.c_uint64), ("score", ctypes.c_uint32),
+                ("leader", ctypes.c_uint32)]
+
+
 _lib = None
 
 # every symbol include/gwa.h declares (checked by tests/test_cabi.py)
@@ -210,6 +245,8 @@ EXPORTS = ["gwa_config_default", "gwa_last_error", "gwa_device_count", "gwa_inde
            "gwa_bam_header_sorted", "gwa_batch_format_bam_sorted", "gwa_batch_results_bam_sorted", "gwa_batch_bam_sort_times",
            "gwa_bam_sorter_open", "gwa_bam_sorter_add_batch", "gwa_bam_sorter_add_records", "gwa_bam_sorter_finish",
            "gwa_bam_sorter_close", "gwa_pipeline_set_sort", "gwa_pipeline_sort_stats",
+           "gwa_bam_sorter_set_markdup", "gwa_bam_sorter_markdup_stats", "gwa_batch_results_bam_dupinfo",
+           "gwa_bam_markdup_timed", "gwa_bam_records_dupinfo", "gwa_pipeline_set_markdup", "gwa_pipeline_markdup_stats",
            "gwa_pipeline_set_output",
            "gwa_pipeline_open", "gwa_pipeline_align", "gwa_pipeline_align_file", "gwa_pipeline_align_file_range",
            "gwa_pipeline_align_pair_files", "gwa_pipeline_align_pairs", "gwa_reads_shard_range", "gwa_pipeline_stats",
@@ -277,6 +314,14 @@ def lib():
             L.gwa_bam_sorter_close.argtypes = [V]
             L.gwa_pipeline_set_sort.argtypes = [V, ctypes.c_char_p, U64, I]
             L.gwa_pipeline_sort_stats.argtypes = [V, P(BamSorterStats)]
+        if hasattr(L, "gwa_bam_sorter_set_markdup"):  # (older libraries in A/B runs lack duplicate marking)
+            L.gwa_bam_sorter_set_markdup.argtypes = [V, I]
+            L.gwa_bam_sorter_markdup_stats.argtypes = [V, P(MarkdupStats)]
+            L.gwa_batch_results_bam_dupinfo.argtypes = [V, P(V), P(U64)]
+            L.gwa_bam_markdup_timed.argtypes = [I, ctypes.c_char_p, U64, I, P(U64), P(ctypes.c_double)]
+            L.gwa_bam_records_dupinfo.argtypes = [I, ctypes.c_char_p, U64, P(V), P(U64)]
+            L.gwa_pipeline_set_markdup.argtypes = [V, I]
+            L.gwa_pipeline_markdup_stats.argtypes = [V, P(MarkdupStats)]
         L.gwa_pipeline_set_output.argtypes = [V, ctypes.c_uint32]
         L.gwa_reads_parse.argtypes = [ctypes.c_char_p, U64, I, I, P(_ReadBuf), P(U64)]
         L.gwa_reads_free.argtypes = [P(_ReadBuf)]
@@ -446,11 +491,23 @@ class BamSorter:
     sorted stream's BGZF blocks to fd_bam and, with fd_bai, the .bai.  device < 0: the host build.  The
     caller frames the file: bgzf_compress(index.bam_header(sorted=True)) before, BGZF_EOF after."""
 
-    def __init__(self, index, device=None, tmp_dir=None, mem=1 << 30):
+    def __init__(self, index, device=None, tmp_dir=None, mem=1 << 30, markdup=False):
         self.h = ctypes.c_void_p()
         dev = index.device if device is None else device
         _check(lib().gwa_bam_sorter_open(index.h, dev, tmp_dir.encode() if tmp_dir is not None else None, mem,
                                          ctypes.byref(self.h)))
+        if markdup:
+            self.set_markdup(True)
+
+    def set_markdup(self, on=True):
+        """duplicate marking (include/gwa.h "Duplicate marking") for the runs added from now on"""
+        _check(lib().gwa_bam_sorter_set_markdup(self.h, 1 if on else 0))
+
+    def markdup_stats(self):
+        """MarkdupStats of the last finish"""
+        st = MarkdupStats()
+        _check(lib().gwa_bam_sorter_markdup_stats(self.h, ctypes.byref(st)))
+        return st
 
     def add_batch(self, run_id, batch):
         _check(lib().gwa_bam_sorter_add_batch(self.h, run_id, batch.h))
@@ -682,6 +739,16 @@ class Pipeline:
         _check(lib().gwa_pipeline_set_sort(self.h, tmp_dir.encode() if tmp_dir is not None else None, mem,
                                            -1 if index is None else index))
 
+    def set_markdup(self, on=True):
+        """Duplicate marking (include/gwa.h "Duplicate marking") in the sorted file calls from now on
+        (gwa_pipeline_set_markdup: after set_sort only)."""
+        _check(lib().gwa_pipeline_set_markdup(self.h, 1 if on else 0))
+
+    def markdup_stats(self):
+        st = MarkdupStats()
+        _check(lib().gwa_pipeline_markdup_stats(self.h, ctypes.byref(st)))
+        return st
+
     def sort_stats(self):
         st = BamSorterStats()
         _check(lib().gwa_pipeline_sort_stats(self.h, ctypes.byref(st)))
@@ -864,6 +931,17 @@ class Batch:
         finally:
             lib().gwa_free(out)
             lib().gwa_free(keys)
+
+    def results_bam_dupinfo(self):
+        """[(endKey, mateKey, score, leader)] of the records of results_bam_sorted(), in that order
+        (gwa_batch_results_bam_dupinfo; include/gwa.h "Duplicate marking")."""
+        import struct
+        out, r = ctypes.c_void_p(), ctypes.c_uint64()
+        _check(lib().gwa_batch_results_bam_dupinfo(self.h, ctypes.byref(out), ctypes.byref(r)))
+        try:
+            return list(struct.iter_unpack("<QQII", ctypes.string_at(out, 24 * r.value)))
+        finally:
+            lib().gwa_free(out)
 
     def bam_sort_times(self):
         t = BamSortTimes()

@@ -38,6 +38,8 @@ last, equal keys in input order) under an "@HD VN:1.6 SO:coordinate" header: eve
 the sorted runs are kept in host memory up to --sort-mem BYTES and spilled to --tmp-dir DIR beyond it, and
 merged into one BGZF stream when the input ends.  --index (with -o FILE) also writes FILE.bai.  --sort refuses
 --shard and --sync (shards would be sorted apart) and --warm-passes above 1; -q sorts its one batch.
+--markdup (with --bam --sort) sets FLAG 0x400 on duplicate templates (include/gwa.h "Duplicate marking": equal
+unclipped 5' ends and strands, the highest quality sum kept), decided on the device from the input-order stream.
 
 Two read files (or one with --interleaved) are paired-end input: mate i of the first file with mate i
 of the second, two SAM lines per pair, streamed through the same pipeline on every device of
@@ -177,6 +179,8 @@ def build_parser():
                         "--shard or --sync (shards would be sorted apart) and not with --warm-passes above 1, which is "
                         "refused")
     a.add_argument("--index", action="store_true", help="with --sort and -o FILE: write the index FILE.bai")
+    a.add_argument("--markdup", action="store_true",
+                   help="with --bam --sort: mark duplicate templates with FLAG 0x400 (include/gwa.h \"Duplicate marking\")")
     a.add_argument("--sort-mem", type=int, default=4 << 30, metavar="BYTES",
                    help="--sort: bytes of records kept in host memory before sorted runs spill to --tmp-dir")
     a.add_argument("--tmp-dir", default=None, metavar="DIR", help="--sort: where runs beyond --sort-mem are spilled")
@@ -298,6 +302,9 @@ def align(ns, out=sys.stdout):
         raise gwa.GwaError("--sort needs --bam")
     if index and not (sort and ns.out is not None):
         raise gwa.GwaError("--index needs --sort and -o FILE (the index is written to FILE.bai)")
+    markdup = getattr(ns, "markdup", False)
+    if markdup and not (bam and sort):
+        raise gwa.GwaError("--markdup needs --bam --sort (duplicates are marked in the sorted file)")
     if sort and (ns.shard is not None or ns.sync):
         raise gwa.GwaError("--sort does not combine with --shard or --sync: the shards would be sorted apart")
     if sort and ns.warm_passes > 1:
@@ -352,7 +359,7 @@ def align(ns, out=sys.stdout):
                     qb.run()
                     if sort:  # its one batch through the sorter: blocks (and the index) by way of a file
                         out.flush()
-                        sorter = gwa.BamSorter(fms[0], tmp_dir=ns.tmp_dir, mem=ns.sort_mem)
+                        sorter = gwa.BamSorter(fms[0], tmp_dir=ns.tmp_dir, mem=ns.sort_mem, markdup=markdup)
                         try:
                             sorter.add_batch(0, qb)
                             if index and not ns.silent:  # (the index holds offsets of FILE: written in place)
@@ -383,6 +390,8 @@ def align(ns, out=sys.stdout):
             try:
                 if sort:
                     pipe.set_sort(tmp_dir=ns.tmp_dir, mem=ns.sort_mem, index=bai.fileno() if bai else None)
+                    if markdup:
+                        pipe.set_markdup(True)
                 # --warm-passes N: N - 1 untimed passes over the file into /dev/null first (pinned buffers,
                 # device caches and the page cache warm), then the timed pass that writes the SAM
                 for _ in range(max(0, ns.warm_passes - 1)):
@@ -416,6 +425,12 @@ def align(ns, out=sys.stdout):
                                       "%.2fs, copy %.2fs, compress %.2fs, write %.2fs, index %.2fs; %d blocks"
                                       % (ss.records, ss.runs, ss.spilled_runs, ss.add_s, ss.order_s, ss.copy_s, ss.compress_s,
                                          ss.write_s, ss.index_s, ss.blocks), file=sys.stderr)
+                            if markdup:
+                                ms = pipe.markdup_stats()
+                                print("[gwa] markdup: %d templates (%d pair, %d fragment), duplicates: %d pair and %d "
+                                      "fragment templates, %d records; keys %.3fs (summed over batches), resolve %.3fs"
+                                      % (ms.templates, ms.pair_templates, ms.frag_templates, ms.dup_pair_templates,
+                                         ms.dup_frag_templates, ms.dup_records, ms.keys_s, ms.resolve_s), file=sys.stderr)
                             if st.inflate_blocks or st.in_bytes:
                                 print("[gwa] BGZF input: %d compressed bytes read, %d members inflated on the device, "
                                       "inflate %.2fs (a part of read)" % (st.in_bytes, st.inflate_blocks, st.inflate_s),

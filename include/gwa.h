@@ -412,6 +412,61 @@ int gwa_bam_sorter_add_records(gwa_bam_sorter_t *s, uint64_t run_id, const uint8
  * non-seekable fd_bam is refused.  No run: no block, and an index of empty contigs.  The runs are consumed. */
 int gwa_bam_sorter_finish(gwa_bam_sorter_t *s, int fd_bam, int fd_bai, gwa_bam_sorter_stats_t *stats);
 void gwa_bam_sorter_close(gwa_bam_sorter_t *s);
+/* ---- Duplicate marking: FLAG 0x400 set in the sorted file, decided on the device ----
+ * Off by default; with it off every byte stays as above.  The reference has nothing here.  The rule is a
+ * function of the input-order record stream alone: run ids ascending, inside a run the order in which the
+ * records were handed over.
+ * Participating record.  FLAG & (0x4 | 0x100 | 0x800) == 0 and refID >= 0.  Every other record is never marked
+ *   and never influences a decision.
+ * End key of a participating record.  u5 is the unclipped 5' coordinate, in int64: forward (FLAG & 0x10 == 0)
+ *   pos - (the sum of the leading S and H elements); reverse pos + reflen + (the sum of the trailing S and H
+ *   elements) - 1, reflen summed over M, D, N, = and X (no max(., 1)).  Leading and trailing: the maximal run of
+ *   S/H elements at that end of the CIGAR; n_cigar_op == 0 gives u5 = pos on either strand.
+ *   endKey = (uint64)(uint32)refID << 33 | (uint64)(uint32)((uint32)u5 + 0x80000000) << 1 | strand (u5 mod 2^32).
+ * Templates.  Records i and i + 1 of one run's input order are a pair when both have FLAG 0x1, neither has
+ *   0x100 or 0x800, i has 0x40 and not 0x80, i + 1 has 0x80 and not 0x40, and their l_read_name and name bytes
+ *   are equal.  Every record not in a pair is a template of its own.  A pair never spans two runs: the batch
+ *   writer never splits a unit, and a caller of gwa_bam_sorter_add_records who cuts a pair across two runs gets
+ *   two single-record templates.  The two pieces of a split single-end read print as 0x1|0x40 and 0x1|0x80
+ *   and are therefore a pair: intended.
+ * Classes.  A pair with both records participating is a pair template, its signature (lo, hi): the two end
+ *   keys ascending.  A template with exactly one participating record (an unpaired record, or a pair with one
+ *   participating record) is a fragment template, its signature that record's endKey.  A template without a
+ *   participating record is in neither class.
+ * Score.  The sum over the template's participating records of the quality bytes q with 15 <= q <= 93 (a
+ *   0xFF byte counts 0), held in a uint32.
+ * Ordinal.  (run_id, input ordinal of the template's first record in the run), compared lexicographically: the
+ *   global input order, whatever the batch size.
+ * Decision.  Among pair templates with equal (lo, hi) the one with the highest score is kept, a tie goes to
+ *   the lowest ordinal; the others are duplicates.  Among fragment templates with equal endKey: if any
+ *   participating record of any pair template has that endKey, all of them are duplicates; otherwise the
+ *   highest score is kept, ties to the lowest ordinal, the others are duplicates.  A duplicate template gets
+ *   FLAG |= 0x400 on each of its participating records and on nothing else; no other byte of any record
+ *   changes.  No optical duplicates, no libraries or read groups, no removal of records.
+ * File.  As "Sorted BAM": order, slices and blocks unchanged (the flag is not part of the key), the .bai of the
+ *   same structure (only its virtual offsets may move, as the blocks' sizes change with the bytes).  File and
+ *   index depend on the record stream only: not on the batch size, the workers, the devices, the memory limit,
+ *   spilling, or the device against the host build. */
+/* Marking for the runs added from now on; fails once a run has been added (until the next finish). */
+int gwa_bam_sorter_set_markdup(gwa_bam_sorter_t *s, int on);
+typedef struct {
+  uint64_t templates, pair_templates, frag_templates, dup_pair_templates, dup_frag_templates, dup_records;
+  double keys_s, resolve_s; /* keys_s: the per-run passes (device: between HIP events), summed over the adds;
+                             * resolve_s: the global resolve inside finish, with its copies */
+} gwa_markdup_stats_t;
+/* Of the last finish (all zero when marking was off). */
+int gwa_bam_sorter_markdup_stats(const gwa_bam_sorter_t *s, gwa_markdup_stats_t *st);
+/* Per record of gwa_batch_results_bam_sorted, in the same order, 24 bytes: endKey (u64; all ones: the record
+ * does not participate), mateKey (u64; the other record's endKey in a pair template with both participating,
+ * else all ones), score (u32, the template's), leader (u32, the batch-input ordinal of the template's first
+ * record).  Library-owned host memory (gwa_free). */
+int gwa_batch_results_bam_dupinfo(gwa_batch_t *b, uint8_t **info, uint64_t *n_records);
+/* The same entries for caller records (validated as gwa_bam_sorter_add_records does), in input order, leader =
+ * the input ordinal: the per-run pass on `device`, or its host build for device < 0; identical bytes. */
+int gwa_bam_records_dupinfo(int device, const uint8_t *records, uint64_t len, uint8_t **info, uint64_t *n_records);
+/* For timing the per-run kernel alone: the records (a valid block_size chain) resident in HBM, the kernel
+ * launched `repeat` times; *kernel_ms = the last launch between HIP events, *n = the records. */
+int gwa_bam_markdup_timed(int device, const uint8_t *records, uint64_t len, int repeat, uint64_t *n, double *kernel_ms);
 /* SAM for reads [first, first+count) only (n_reads = count). */
 int gwa_batch_results_range(gwa_batch_t *b, uint32_t first, uint32_t count, gwa_results_t *out);
 void gwa_batch_free(gwa_batch_t *b);
@@ -533,6 +588,11 @@ int gwa_pipeline_set_output(gwa_pipeline_t *p, uint32_t format);
  * gwa_pipeline_sort_stats gives the sorter's counters and times of the last such call. */
 int gwa_pipeline_set_sort(gwa_pipeline_t *p, const char *tmp_dir, uint64_t mem_bytes, int bai_fd);
 int gwa_pipeline_sort_stats(const gwa_pipeline_t *p, gwa_bam_sorter_stats_t *st);
+/* Duplicate marking ("Duplicate marking" above) in the sorted file calls from now on: valid only while the
+ * pipeline sorts (gwa_pipeline_set_sort).  gwa_pipeline_markdup_stats gives the counts and times of the last
+ * sorted call. */
+int gwa_pipeline_set_markdup(gwa_pipeline_t *p, int on);
+int gwa_pipeline_markdup_stats(const gwa_pipeline_t *p, gwa_markdup_stats_t *st);
 int gwa_pipeline_stats(const gwa_pipeline_t *p, gwa_pipeline_stats_t *st);
 void gwa_pipeline_close(gwa_pipeline_t *p);
 
